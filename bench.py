@@ -2,6 +2,11 @@
 """Headline benchmark: directed-edge flow updates/s + % HBM roofline; rounds to 1e-9 error.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|er|rgg-dist|pairwise|...]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: setup, warmup, the K timed steps,
+the result line. `--full` adds everything else the benchmark measures (see below).
+`--dump-outputs DIR` writes what the timed steps computed as DIR/<name>.npy after them.
 
 N = 1 (default workload "er", BASELINE.json configs[1]): Erdos-Renyi G(n=1,000,000,
 m=4,000,000), self-loops dropped, deduplicated, symmetrised (E ~ 8.0e6 directed edges); node
@@ -25,8 +30,16 @@ end, between barriers; value = edge updates of all ranks / max-over-ranks wall t
 
 Printed by rank 0: ONE JSON line, with `roofline` (the round kernel's algorithmic bytes
 24E + 28N per launch, §8(d), / the mean device time of rounds 1 .. K-1 from those events,
-against 8 TB/s; `traffic` from the PMC passes in profiles/ when they match this command) and
-`cpu_baseline` (the C port of the oracle on the host, single thread, bounded sample).
+against 8 TB/s; `traffic` from the PMC passes in profiles/ when they match this command).
+
+With `--full` the line also carries what takes runs of its own, all untimed and after the
+timed region: `cpu_baseline` (the C port of the oracle on the host, single thread, bounded
+sample), rounds to 1e-9 (a convergence run with the error check every round), `host_io` (the
+result's way back to the host), the device's copy rate beside the roofline, and at N = 1 with
+the default workload BASELINE configs 2 (as written), 3, 4 and 5's per-GPU unit measured
+beside the headline. --no-conv, --cpu-seconds 0 and --no-unit switch parts of that off. The
+rgg-dist lines (N > 1) are the same with and without `--full`: their RCCL parity check guards
+the line and stays, and so does their convergence run unless --no-conv is given.
 """
 from __future__ import annotations
 
@@ -85,7 +98,19 @@ def parse(argv=None):
                          "long (default 25 ms; at N > 1 a fixed round count, the same on every rank)")
     ap.add_argument("--no-unit", action="store_true",
                     help="N = 1 default line without its weak_scaling_unit (config 5's per-GPU RGG)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, rounds "
+                         "to 1e-9, host_io, the copy rate and, at N = 1 with the default workload, "
+                         "BASELINE configs 2-5 beside the headline (--no-conv, --cpu-seconds 0 and "
+                         "--no-unit switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (estimates, flows) to "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of "
+                         "a larger array)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port() -> int:
@@ -114,6 +139,34 @@ def chunk_bounds(steps: int, nchunk: int = 10):
     rest = steps - 1
     k = 1 if steps <= 100 else min(nchunk, rest)
     return [0] + [1 + rest * q // k for q in range(k + 1)]
+
+
+DUMP_BUDGET = 60_000_000  # bytes --dump-outputs writes, all files together (the limit is 64 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: each of `arrays` ({name: array}) as outdir/<name>.npy in float64. The
+    budget is shared smallest first (an array below its share is written whole and leaves the
+    rest to the others); a larger one is sampled, one element from each of as many equal
+    strata as fit, at offsets from a generator seeded with DUMP_SEED, so the same command
+    samples the same elements in every run and build. Returns {name: [elements written,
+    elements in all]}."""
+    os.makedirs(outdir, exist_ok=True)
+    left, written = budget - 128 * len(arrays), {}  # 128 B: each file's .npy header
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    for k, (name, a) in enumerate(todo):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        share = left // (len(todo) - k) // 8
+        if a.size > share:  # one element of each of `share` equal strata, at a seeded offset
+            lo = np.arange(share, dtype=np.int64) * a.size // share
+            out = a[lo + np.random.default_rng(DUMP_SEED).integers(0, a.size // share, share)]
+        else:
+            out = a
+        np.save(os.path.join(outdir, name + ".npy"), out)
+        left -= out.nbytes
+        written[name] = [int(out.size), int(a.size)]
+    return written
 
 
 def main():
@@ -150,6 +203,10 @@ def main():
     if wl == "rgg-dist":
         return run_dist(args, world, rank, local, dist)
     if wl == "pairwise" and world > 1:  # the tick replay does not shard: replicas
+        if args.dump_outputs:
+            print("[bench] error: --dump-outputs with pairwise replicas (every replica computes the "
+                  "N = 1 run's arrays: dump those)", file=sys.stderr, flush=True)
+            sys.exit(2)
         return run_pairwise_replicas(args, world, rank, local, dist)
     if world > 1:
         print(f"[bench] error: workload {wl} is single-GPU (use rgg-dist at N > 1)", file=sys.stderr, flush=True)
@@ -315,40 +372,46 @@ def run_single(args, wl):
     t_setup = time.perf_counter() - t_setup
 
     wall, phases, roof, value_r1, kinfo, kname = measure_window(eng, g, args.steps)
-    t_down = time.perf_counter()  # the K-round job's result back to the host (fu_get_estimates)
-    eng.estimates()
-    t_down = time.perf_counter() - t_down
-    t_down2 = time.perf_counter()  # again: a snapshot's cost once the bounce buffers exist
-    eng.estimates()
-    t_down2 = time.perf_counter() - t_down2
     pack_after = eng.pack_widths()[2]
     value = g.E * args.steps / wall
-    host_io = {"create_s": t_create, "estimates_to_host_s": t_down, "estimates_to_host_again_s": t_down2,
-               "host_bytes_in": 8 * (g.n + 1) + 4 * g.E + 8 * g.n, "host_bytes_out": 8 * g.n,
-               "value_with_create_and_download": g.E * args.steps / (wall + t_create + t_down),
-               "note": "not the metric: the handle is created once per job (fu_create: the CSR and values "
-                       "cross PCIe, the launch plans are built on the host) and the estimates return once"}
-    companions = args.workload == "auto" and not args.no_unit
+    host_io = None
+    if args.full:
+        t_down = time.perf_counter()  # the K-round job's result back to the host (fu_get_estimates)
+        eng.estimates()
+        t_down = time.perf_counter() - t_down
+        t_down2 = time.perf_counter()  # again: a snapshot's cost once the bounce buffers exist
+        eng.estimates()
+        t_down2 = time.perf_counter() - t_down2
+        host_io = {"create_s": t_create, "estimates_to_host_s": t_down, "estimates_to_host_again_s": t_down2,
+                   "host_bytes_in": 8 * (g.n + 1) + 4 * g.E + 8 * g.n, "host_bytes_out": 8 * g.n,
+                   "value_with_create_and_download": g.E * args.steps / (wall + t_create + t_down),
+                   "note": "not the metric: the handle is created once per job (fu_create: the CSR and values "
+                           "cross PCIe, the launch plans are built on the host) and the estimates return once"}
+    dumped = None
+    if args.dump_outputs:  # the state after round K-1, before anything below moves the engine on
+        dumped = dump_outputs(args.dump_outputs, {"estimates": eng.estimates(), "flows": eng.flows()})
+    companions = args.full and args.workload == "auto" and not args.no_unit
     extra = {}
     if companions and args.steps != 1000:  # BASELINE config 2 as written, on the same engine
         extra["config2_1000"] = guarded("config2_1000", config2_1000, eng, g, args.kernel)
 
     conv = {"rounds_to_1e-9": None, "err_after_conv_rounds": None, "conv_rounds": None,
             "components": None}
-    if not args.no_conv:  # rounds to 1e-9 vs the per-component means (untimed)
+    if args.full and not args.no_conv:  # rounds to 1e-9 vs the per-component means (untimed)
         conv = convergence(eng, g.rowptr, g.col, v, args.conv_rounds)
     eng.close()
-    # the box's own streaming rate, measured in this run (untimed, after the timed region and
-    # with the engine freed): a float4 copy of 1 GB, so a slow box shows as a slow copy as well
-    # as a slow round
-    try:
-        roof["copy_GBs"] = fu.copy_bandwidth(device, 1 << 30, 5)
-        roof["frac_of_copy"] = roof["achieved"] / roof["copy_GBs"]
-    except Exception as ex:  # noqa: BLE001  (the headline line must survive)
-        print(f"[bench] copy_bandwidth failed: {ex!r}", file=sys.stderr, flush=True)
-        roof["copy_GBs"] = None
-        roof["copy_error"] = repr(ex)
-    cpu = cpu_baseline(g, v, args.cpu_seconds) if args.cpu_seconds > 0 else None
+    if args.full:
+        # the box's own streaming rate, measured in this run (untimed, after the timed region and
+        # with the engine freed): a float4 copy of 1 GB, so a slow box shows as a slow copy as well
+        # as a slow round
+        try:
+            roof["copy_GBs"] = fu.copy_bandwidth(device, 1 << 30, 5)
+            roof["frac_of_copy"] = roof["achieved"] / roof["copy_GBs"]
+        except Exception as ex:  # noqa: BLE001  (the headline line must survive)
+            print(f"[bench] copy_bandwidth failed: {ex!r}", file=sys.stderr, flush=True)
+            roof["copy_GBs"] = None
+            roof["copy_error"] = repr(ex)
+    cpu = cpu_baseline(g, v, args.cpu_seconds) if args.full and args.cpu_seconds > 0 else None
     out = {
         "metric": METRIC, "value": value, "unit": "edge-updates/s", "n_gpus": 1,
         "value_rounds_1_on": value_r1,
@@ -369,7 +432,10 @@ def run_single(args, wl):
             "parallelism": "single GPU",
         },
         "roofline": roof, "cpu_baseline": cpu, "graph_gen_s": t_gen, "host_io": host_io,
+        "full": args.full,
     }
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     out.update(conv)
     del g
     if companions:
@@ -443,7 +509,7 @@ def rmat24_unit(args):
 def pairwise_unit(args):
     """BASELINE config 3 beside the headline: RR-64K pairwise tick replay, ticks 101-500."""
     a = argparse.Namespace(**vars(args))
-    a.n, a.steps, a.warmup, a.cpu_seconds = 0, 400, 50, 0
+    a.n, a.steps, a.warmup, a.cpu_seconds, a.dump_outputs = 0, 400, 50, 0, None
     line = pairwise_line(a)
     return {"workload": line["config"]["workload"], "value": line["value"], "unit": line["unit"],
             "ms_per_step": line["ms_per_step"],
@@ -584,6 +650,9 @@ def run_parts(args):
     kinfo = engs[0].info()
     fr, tot = fu.mem_info(0)  # while the partitions are resident
     free = [fr / 2 ** 30, tot / 2 ** 30]
+    dumped = None
+    if args.dump_outputs:  # every partition's estimates after round K-1 (its own rows)
+        dumped = dump_outputs(args.dump_outputs, {f"estimates_part{r}": e.estimates() for r, e in enumerate(engs)})
     for e in engs:
         e.close()
     line = {
@@ -603,7 +672,7 @@ def run_parts(args):
                      "alg_bytes_per_launch": alg, "avg_launch_us": per_round * 1e6,
                      "kernel": "k_round_recon per partition (own streams), halo copies on the comm streams",
                      "launch_window": f"rounds 0-{args.steps - 1} (round 0 included), the slowest partition's events"},
-        "cpu_baseline": None,
+        "cpu_baseline": None, "full": args.full, "outputs_dumped": dumped,
     }
     print(json.dumps(line), flush=True)
 
@@ -613,7 +682,7 @@ def weak_unit(args):
     partitioned path, one rank, the same steps and warmup), measured live in the same run, so
     that the driver's N > 1 lines (which run that workload) have their one-GPU counterpart."""
     a = argparse.Namespace(**vars(args))
-    a.n, a.kernel, a.no_conv, a.strong = 0, "auto", True, False
+    a.n, a.kernel, a.no_conv, a.strong, a.dump_outputs = 0, "auto", True, False, None
     line = measure_dist(a, 1, 0, 0, None)
     return {"workload": line["config"]["workload"], "value": line["value"], "unit": line["unit"],
             "ms_per_step": line["ms_per_step"], "E_directed": line["config"]["E_directed"],
@@ -673,6 +742,10 @@ def measure_dist(args, world, rank, local, dist):
     barrier()
     wall, dev_ms, b = timed_rounds(eng, args.steps)
     barrier()
+    dumped = None
+    if args.dump_outputs:  # this rank's rows after round K-1, the budget split over the ranks
+        dumped = dump_outputs(args.dump_outputs, {f"estimates_rank{rank}": eng.estimates(),
+                                                  f"flows_rank{rank}": eng.flows()}, DUMP_BUDGET // world)
     # the halo's device time per round (untimed): one round per call, then its halo events
     hs = []
     for _ in range(20):
@@ -707,6 +780,9 @@ def measure_dist(args, world, rank, local, dist):
                          halo_us=halo_us, round_us=1e3 * dev1 / max(1, args.steps - 1), t_gen=t_gen,
                          conv=conv, strong=args.strong, rccl_parity=parity, traffic=traffic)
         line["config"]["settle_rounds"] = n_settle  # untimed, right before the window, every rank
+        line["full"] = args.full
+        if dumped is not None:
+            line["outputs_dumped"] = dumped  # rank 0's files; every rank writes its own
     eng.close()
     return line
 
@@ -876,9 +952,13 @@ def pairwise_line(args, device=0, barrier=None):
     wall = time.perf_counter() - t
     if barrier:
         barrier()
+    dumped = None
+    if args.dump_outputs and barrier is None:  # the replay's state after the last timed tick
+        last, fl, es = rep.state()
+        dumped = dump_outputs(args.dump_outputs, {"last_avg": last, "flows": fl, "estimates": es})
     rep.close()
     cpu = None
-    if args.cpu_seconds > 0 and device == 0 and barrier is None:
+    if args.full and args.cpu_seconds > 0 and device == 0 and barrier is None:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import coracle
 
@@ -903,7 +983,7 @@ def pairwise_line(args, device=0, barrier=None):
                      "traffic": pmc_traffic(g.n, g.E, "pairwise", args.steps) if args.warmup == 50 else None,
                      "alg_bytes_per_launch": alg, "kernel": "k_replay_persist_reg",
                      "avg_launch_us": ms * 1e3, "launch_window": f"one launch, {args.steps} ticks"},
-        "cpu_baseline": cpu}
+        "cpu_baseline": cpu, "full": args.full, "outputs_dumped": dumped}
 
 
 def cpu_baseline(g, v, seconds):

@@ -221,12 +221,7 @@ class _FakeReplay:
         pass
 
 
-def test_n1_line_carries_config2_rmat24_pairwise_units(monkeypatch, capsys):
-    """The driver's N = 1 command (--steps 20 --warmup 5) measures BASELINE configs 2 (as
-    written: 1000 rounds), 4 (R-MAT-24) and 3 (pairwise RR-64K, ticks 101-500) beside the
-    headline, each guarded so that a failure keeps the headline line (CPU: fake engines)."""
-    import json
-
+def _fake_single_gpu(monkeypatch):
     import fu
 
     graphs = {"er": _FakeGraph(1_000_000, 7_999_972), "rmat": _FakeGraph(1 << 24, 520_761_504)}
@@ -239,7 +234,16 @@ def test_n1_line_carries_config2_rmat24_pairwise_units(monkeypatch, capsys):
         "config": {"workload": "rgg", "E_directed": 1, "kernel_selected": "recon", "tile_selected": (1024, 128)},
         "value": 1.0, "unit": "edge-updates/s", "ms_per_step": 1.0,
         "roofline": {"frac": 0.7, "avg_launch_us": 300.0}})
-    args = bench.parse(["--steps", "20", "--warmup", "5", "--no-conv", "--cpu-seconds", "0"])
+
+
+def test_n1_line_carries_config2_rmat24_pairwise_units(monkeypatch, capsys):
+    """The driver's N = 1 command with --full (--steps 20 --warmup 5) measures BASELINE configs
+    2 (as written: 1000 rounds), 4 (R-MAT-24) and 3 (pairwise RR-64K, ticks 101-500) beside the
+    headline, each guarded so that a failure keeps the headline line (CPU: fake engines)."""
+    import json
+
+    _fake_single_gpu(monkeypatch)
+    args = bench.parse(["--steps", "20", "--warmup", "5", "--no-conv", "--cpu-seconds", "0", "--full"])
     bench.run_single(args, "er")
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert line["steps"] == 20 and line["roofline"]["copy_GBs"] == 5500.0
@@ -266,6 +270,61 @@ def test_n1_line_carries_config2_rmat24_pairwise_units(monkeypatch, capsys):
     bench.run_single(args, "er")
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert "ZeroDivisionError" in line["rmat24_unit"]["error"] and line["value"] > 0
+
+
+def test_plain_n1_run_is_lean_and_dumps_outputs(monkeypatch, capsys, tmp_path):
+    """Without --full the N = 1 command does what its headline needs and nothing else: no
+    companion measurement, convergence run, CPU baseline or copy-rate run is even started, the
+    headline fields are there, and --dump-outputs writes the engine's estimates and flows after
+    the last timed round as float64 .npy files (CPU: fake engines)."""
+    import json
+
+    import fu
+
+    _fake_single_gpu(monkeypatch)
+
+    def never(*a, **k):
+        raise AssertionError("a plain run started a --full measurement")
+
+    for name in ("config2_1000", "weak_unit", "rmat24_unit", "pairwise_unit", "convergence", "cpu_baseline",
+                 "measure_dist"):
+        monkeypatch.setattr(bench, name, never)
+    monkeypatch.setattr(fu, "copy_bandwidth", never)
+    monkeypatch.setattr(_FakeEngine, "flows", lambda self: np.arange(self.r, dtype=np.float32), raising=False)
+    out = tmp_path / "dump"
+    args = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)])
+    assert args.full is False and bench.parse(["--full"]).full is True
+    bench.run_single(args, "er")
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["metric"] == bench.METRIC and line["unit"] == "edge-updates/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["steps"] == 20 and line["full"] is False
+    assert line["value"] > 0 and abs(line["ms_per_step"] - 7_999_972 * 1e3 / line["value"]) < 1e-9 * line["ms_per_step"]
+    assert abs(line["roofline"]["avg_launch_us"] - 50.0) < 1e-9  # from the window's own events
+    for key in ("config2_1000", "weak_scaling_unit", "rmat24_unit", "pairwise_unit"):
+        assert key not in line
+    assert line["cpu_baseline"] is None and line["host_io"] is None and line["rounds_to_1e-9"] is None
+    assert "copy_GBs" not in line["roofline"]
+    est, fl = np.load(out / "estimates.npy"), np.load(out / "flows.npy")
+    assert est.dtype == np.float64 and fl.dtype == np.float64
+    assert np.array_equal(est, np.zeros(4)) and np.array_equal(fl, np.arange(20.0))  # after round 19
+    assert line["outputs_dumped"] == {"estimates": [4, 4], "flows": [20, 20]}
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs stays within its budget: small arrays whole, a larger one as a sample
+    that is the same in every run (seeded), in order, one element per stratum."""
+    big = np.arange(1000, dtype=np.float64)
+    small = np.arange(10, dtype=np.float32)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small}, budget=256 + 8 * 110)
+    assert w == {"small": [10, 10], "big": [100, 1000]}
+    a = np.load(tmp_path / "a" / "big.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.astype(np.float64))
+    assert a.dtype == np.float64 and np.array_equal(a // 10, np.arange(100.0))
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big, "small": small}, budget=256 + 8 * 110)
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), a)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 256 + 8 * 110
+    assert bench.DUMP_BUDGET <= 64_000_000
 
 
 def test_window_stats_lookup(tmp_path, monkeypatch):
