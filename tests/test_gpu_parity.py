@@ -13,6 +13,7 @@ import coracle
 import fu
 from conftest import (ca_sync_fixtures, fixture_decl_csr, load_json, load_npz, tick_fixtures,
                       write_deployment_xml, write_platform_xml)
+from parity_util import _class_edge_graph, _er_with_outlier_pairs, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,8 +32,8 @@ def _check_fixture(meta, kernel, hub_threshold=None):
     for k, r in enumerate(rounds):
         eng.run(r + 1 - done)
         done = r + 1
-        assert np.array_equal(eng.estimates(), d["last_avg"][k]), (meta["file"], kernel, r)
-        assert np.array_equal(eng.flows(), d["flows"][k]), (meta["file"], kernel, r)
+        assert_same_bits(eng.estimates(), d["last_avg"][k], (meta["file"], kernel, r))
+        assert_same_bits(eng.flows(), d["flows"][k], (meta["file"], kernel, r))
     eng.close()
 
 
@@ -57,8 +58,8 @@ def test_er_vs_c_oracle_bitwise(kernel):
     eng = fu.CollectAll(g, v, kernel=kernel)
     eng.run(40)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 40, nthreads=8)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -69,8 +70,8 @@ def test_rmat_hubs_vs_c_oracle_bitwise(kernel):
     eng = fu.CollectAll(g, v, kernel=kernel)
     eng.run(25)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 25, nthreads=8)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_err_trace_and_max_err():
@@ -107,8 +108,8 @@ def test_first_rounds_flows_each_round(kernel):
         for r in range(1, 6):
             eng.run(1)
             a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, r)
-            assert np.array_equal(eng.estimates(), a_ref), (kernel, r)
-            assert np.array_equal(eng.flows(), f_ref), (kernel, r)
+            assert_same_bits(eng.estimates(), a_ref, (kernel, r))
+            assert_same_bits(eng.flows(), f_ref, (kernel, r))
         eng.reset()
     eng.close()
 
@@ -145,8 +146,8 @@ def test_isolated_and_empty():
     eng = fu.CollectAll(rowptr=rp, col=col, values=v)
     eng.run(5)
     a_ref, f_ref = coracle.ca_sync(rp, col, np.array([1, 0], dtype=np.int32), v, 5)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     assert eng.estimates()[3] == 1e-310
 
 
@@ -209,11 +210,11 @@ def test_replay_rr64k_vs_c_oracle(mode, persistent):
     l_ref, f_ref, e_ref, s_ref = coracle.replay(a["rowptr"], v, a["tick_task_off"], a["tasks"],
                                                 a["events"], a["out_ids"], tr.n_msgs,
                                                 [60, 120, 159])
-    assert np.array_equal(last, l_ref)
-    assert np.array_equal(flows, f_ref)
-    assert np.array_equal(est, e_ref)
+    assert_same_bits(last, l_ref)
+    assert_same_bits(flows, f_ref)
+    assert_same_bits(est, e_ref)
     for t in (60, 120, 159):
-        assert np.array_equal(snaps[t], s_ref[t])
+        assert_same_bits(snaps[t], s_ref[t])
 
 
 def test_headline_window_bitwise():
@@ -229,14 +230,14 @@ def test_headline_window_bitwise():
     bench.prepare(eng, "auto", 5)
     bench.timed_rounds(eng, 20)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 20, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     eng.reset()
     bench.prepare(eng, "auto", 400, [], tune=False)
     bench.timed_rounds(eng, 1000)
     coracle.ca_rounds(g.rowptr, g.col, g.rev, v, 980, a_ref, f_ref, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     eng.close()
 
 
@@ -255,11 +256,12 @@ def test_marked_window_matches_plain_rounds(bounds):
         if bounds[k + 1] > bounds[k]:
             assert eng.elapsed(k, k + 1) > 0.0, k
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, bounds[-1], nthreads=8)
-    assert np.array_equal(eng.estimates(), a_ref) and np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     eng.run_marked(np.asarray([0, 2], dtype=np.int32))
     assert eng.elapsed(0, 1) > 0.0
     coracle.ca_rounds(g.rowptr, g.col, g.rev, v, 2, a_ref, f_ref, nthreads=8)
-    assert np.array_equal(eng.estimates(), a_ref)
+    assert_same_bits(eng.estimates(), a_ref)
     eng.close()
 
 
@@ -279,9 +281,9 @@ def test_pairwise_unit_window_bitwise():
     rep.close()
     l_ref, f_ref, e_ref, _ = coracle.replay(a["rowptr"], v, a["tick_task_off"], a["tasks"], a["events"],
                                             a["out_ids"], tr.n_msgs)
-    assert np.array_equal(last, l_ref)
-    assert np.array_equal(flows, f_ref)
-    assert np.array_equal(est, e_ref)
+    assert_same_bits(last, l_ref)
+    assert_same_bits(flows, f_ref)
+    assert_same_bits(est, e_ref)
 
 
 @pytest.mark.parametrize("mode,tag", [("ca", "fwd"), ("pw", "fwd"), ("ca", "rev"), ("pw", "rand7")])
@@ -349,8 +351,8 @@ def test_full_size_er1m_convergence_and_prefix_parity():
     eng = fu.CollectAll(g, v)
     eng.run(60)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 60, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     tgt, comp = fu.component_means(g.rowptr, g.col, v)
     eng.set_targets(tgt)
     tr = eng.run(940, err_every=10)
@@ -376,8 +378,8 @@ def test_config2_as_written_1000_rounds_bitwise():
             a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, done, nthreads=16)
         else:
             coracle.ca_rounds(g.rowptr, g.col, g.rev, v, k, a_ref, f_ref, nthreads=16)
-        assert np.array_equal(eng.estimates(), a_ref), done
-        assert np.array_equal(eng.flows(), f_ref), done
+        assert_same_bits(eng.estimates(), a_ref, done)
+        assert_same_bits(eng.flows(), f_ref, done)
     assert {32, 16, 8} <= widths, widths  # every packed width ran
     assert eng.info()["rounds"] == 1000
     eng.close()
@@ -396,8 +398,8 @@ def test_dist_single_rank_rccl_matches_engine():
     d.run(30)
     eng = fu.CollectAll(g, v)
     eng.run(30)
-    assert np.array_equal(d.estimates(), eng.estimates())
-    assert np.array_equal(d.flows(), eng.flows())
+    assert_same_bits(d.estimates(), eng.estimates())
+    assert_same_bits(d.flows(), eng.flows())
     tgt, _ = fu.component_means(g.rowptr, g.col, v)
     d.set_targets(tgt)
     tr = d.run(10, err_every=5)
@@ -405,8 +407,8 @@ def test_dist_single_rank_rccl_matches_engine():
     d.close()
     d8 = DistCollectAll(plan, v, unique_id(), kernel="stage")  # kernel 8 at one RCCL rank
     d8.run(30)
-    assert np.array_equal(d8.estimates(), eng.estimates())
-    assert np.array_equal(d8.flows(), eng.flows())
+    assert_same_bits(d8.estimates(), eng.estimates())
+    assert_same_bits(d8.flows(), eng.flows())
     d8.close()
 
 
@@ -436,8 +438,8 @@ def test_dist_ghost_slots_local_transport_bitwise(world, kind, kernel):
     run_local(engs, rounds)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, rounds, nthreads=16)
     for p, e in zip(plans, engs):
-        assert np.array_equal(e.estimates(), a_ref[p.lo:p.hi]), p.rank
-        assert np.array_equal(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]]), p.rank
+        assert_same_bits(e.estimates(), a_ref[p.lo:p.hi], p.rank)
+        assert_same_bits(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]], p.rank)
     for e in engs:
         e.close()
 
@@ -459,12 +461,14 @@ def test_dist_autotune_never_runs_kernel_9():
     assert info["autotune"] == "done" and info["kernel"] in ("recon", "stage"), info
     assert info["tune_us_per_round"]["pregather"] == 0.0
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 120, nthreads=16)
-    assert np.array_equal(d.estimates(), a_ref) and np.array_equal(d.flows(), f_ref)
+    assert_same_bits(d.estimates(), a_ref)
+    assert_same_bits(d.flows(), f_ref)
     d.close()
     d9 = DistCollectAll(plan, v, unique_id(), kernel="pregather")
     d9.run(40)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 40, nthreads=16)
-    assert np.array_equal(d9.estimates(), a_ref) and np.array_equal(d9.flows(), f_ref)
+    assert_same_bits(d9.estimates(), a_ref)
+    assert_same_bits(d9.flows(), f_ref)
     d9.close()
 
 
@@ -494,8 +498,8 @@ def test_dist_rmat_heavy_rows_and_hubs_with_ghosts_bitwise(world, geo):
     run_local(engs, rounds)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, rounds, nthreads=16)
     for p, e in zip(plans, engs):
-        assert np.array_equal(e.estimates(), a_ref[p.lo:p.hi]), p.rank
-        assert np.array_equal(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]]), p.rank
+        assert_same_bits(e.estimates(), a_ref[p.lo:p.hi], p.rank)
+        assert_same_bits(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]], p.rank)
     for e in engs:
         e.close()
 
@@ -522,15 +526,15 @@ def test_dist_kernel9_rmat_ghosts_bitwise(world):
         run_local(engs, rounds - (7 if rounds == 60 else 0))
         a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, rounds, nthreads=16)
         for p, e in zip(plans, engs):
-            assert np.array_equal(e.estimates(), a_ref[p.lo:p.hi]), (p.rank, rounds)
-            assert np.array_equal(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]]), (p.rank, rounds)
+            assert_same_bits(e.estimates(), a_ref[p.lo:p.hi], (p.rank, rounds))
+            assert_same_bits(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]], (p.rank, rounds))
     for e in engs:
         e.reset()
         fu._lib.call("fu_set_option", e._h, b"kernel", 4)
     run_local(engs, 5)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 5, nthreads=16)
     for p, e in zip(plans, engs):
-        assert np.array_equal(e.estimates(), a_ref[p.lo:p.hi]), p.rank
+        assert_same_bits(e.estimates(), a_ref[p.lo:p.hi], p.rank)
     for e in engs:
         e.close()
 
@@ -576,8 +580,8 @@ def test_dist_exchange_local_checks_round_counts():
     run_local(engs, 3)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 5, nthreads=16)
     for p, e in zip(plans, engs):
-        assert np.array_equal(e.estimates(), a_ref[p.lo:p.hi]), p.rank
-        assert np.array_equal(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]]), p.rank
+        assert_same_bits(e.estimates(), a_ref[p.lo:p.hi], p.rank)
+        assert_same_bits(e.flows(), f_ref[g.rowptr[p.lo]:g.rowptr[p.hi]], p.rank)
     for e in engs:
         e.close()
 
@@ -597,8 +601,8 @@ def test_dist_rgg_slabs_local_transport_bitwise():
     eng.run(20)
     a, f = eng.estimates(), eng.flows()
     for p, e in zip(parts, engs):
-        assert np.array_equal(e.estimates(), a[p.lo:p.hi])
-        assert np.array_equal(e.flows(), f[g.rowptr[p.lo]:g.rowptr[p.hi]])
+        assert_same_bits(e.estimates(), a[p.lo:p.hi])
+        assert_same_bits(e.flows(), f[g.rowptr[p.lo]:g.rowptr[p.hi]])
     for e in engs:
         e.close()
 
@@ -616,9 +620,10 @@ def test_replay_with_faults_vs_c_oracle(persistent):
     l_ref, f_ref, e_ref, s_ref = coracle.replay(a["rowptr"], v, a["tick_task_off"], a["tasks"],
                                                 a["events"], a["out_ids"], tr.n_msgs, [60, 149, 299])
     last, flows, est = rep.state()
-    assert np.array_equal(last, l_ref) and np.array_equal(flows, f_ref)
+    assert_same_bits(last, l_ref)
+    assert_same_bits(flows, f_ref)
     for t in (60, 149, 299):
-        assert np.array_equal(snaps[t], s_ref[t])
+        assert_same_bits(snaps[t], s_ref[t])
 
 
 def test_dist_rgg_slab_estimates_only_halo_matches_engine():
@@ -634,8 +639,8 @@ def test_dist_rgg_slab_estimates_only_halo_matches_engine():
     g = fu.Graph.random_geometric(n, avg_deg=8.0, seed=5)
     eng = fu.CollectAll(g, v)
     eng.run(40)
-    assert np.array_equal(d.estimates(), eng.estimates())
-    assert np.array_equal(d.flows(), eng.flows())
+    assert_same_bits(d.estimates(), eng.estimates())
+    assert_same_bits(d.flows(), eng.flows())
 
 
 def test_autotune_switches_kernels_bitwise():
@@ -650,8 +655,8 @@ def test_autotune_switches_kernels_bitwise():
     assert info["autotune"] == "done" and info["rounds"] == 64
     assert all(t > 0 for t in info["tune_us_per_round"].values())
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 64, nthreads=8)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_autotune_width_cache_across_reset_bitwise():
@@ -668,8 +673,8 @@ def test_autotune_width_cache_across_reset_bitwise():
     passes = eng.info()["tune_passes"]
     assert passes >= 3
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 448, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     eng.reset()
     for _ in range(7):
         eng.run(64)
@@ -677,8 +682,8 @@ def test_autotune_width_cache_across_reset_bitwise():
     # widths tuned before the reset reuse their winner; a width whose change the host first
     # saw while a pass was pending (asynchronous width copies) may still need one pass
     assert eng.info()["tune_passes"] - passes <= 1
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_reset_drops_a_width_pass_left_pending():
@@ -705,27 +710,13 @@ def test_reset_drops_a_width_pass_left_pending():
     eng.synchronize()
     assert eng.info()["tune_passes"] == passes
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 64, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     # a pass armed by the kernel option is not dropped by a reset
     eng.reset()
     eng.set_option("kernel", 0)
     eng.reset()
     assert eng.info()["autotune"] == "pending"
-
-
-def _er_with_outlier_pairs(n, m, pairs, seed):
-    """ER(n, m) plus `pairs` disjoint 2-node components whose values are far from the giant
-    component's mean: their estimates never enter the packed window, so every gather of
-    them goes through the escape code."""
-    g = fu.Graph.erdos_renyi(n, m, seed=seed)
-    src = np.repeat(np.arange(g.n), np.diff(g.rowptr))
-    keep = src < g.col
-    ps = n + 2 * np.arange(pairs)
-    s = np.concatenate([src[keep], ps])
-    d = np.concatenate([g.col[keep], ps + 1])
-    v = np.concatenate([fu.uniform_values(n, seed=seed), 1e6 + np.arange(2 * pairs, dtype=np.float64)])
-    return fu.Graph.from_edges(n + 2 * pairs, s, d), v
 
 
 @pytest.mark.parametrize("kind,kernel", [("er", "recon"), ("rmat", "recon"), ("er", "stage"),
@@ -747,14 +738,14 @@ def test_packed_gather_long_run_bitwise(kind, kernel):
         eng.run(25)
         seen.update(eng.pack_widths())
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, rounds, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     assert seen & {8, 16, 32}, seen  # packing was actually exercised
     off = fu.CollectAll(g, v, kernel="recon", hub_threshold=16)
     off.set_option("pack", 0)
     off.run(rounds)
     assert off.pack_widths() == (0, 0, 0)
-    assert np.array_equal(off.estimates(), a_ref)
+    assert_same_bits(off.estimates(), a_ref)
 
 
 @pytest.mark.parametrize("opts", [{"staged_lo": 0}, {"staged_lo": 0, "pack": 0}, {"tr_bpx": 0},
@@ -772,8 +763,8 @@ def test_load_order_and_transpose_options_bitwise(opts):
         eng.set_option(k, val)
     eng.run(rounds)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, rounds, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_packed_gather_with_kernel_switches():
@@ -789,7 +780,8 @@ def test_packed_gather_with_kernel_switches():
         got = (eng.estimates(), eng.flows())
         if ref is None:
             ref = got
-        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), kernel
+        assert_same_bits(got[0], ref[0], kernel)
+        assert_same_bits(got[1], ref[1], kernel)
 
 
 @pytest.mark.parametrize("kernel,opts", [("recon", {"tile_edges": 2048}),
@@ -812,8 +804,8 @@ def test_tile_geometries_bitwise(kernel, opts, kind):
         eng.set_option(k, val)
     eng.run(30)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 30, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 @pytest.mark.parametrize("layout", [0, 1, 2, 3])
@@ -832,8 +824,8 @@ def test_stage_forced_layouts_bitwise(layout):
         eng.run(25)
         seen.update(eng.pack_widths())
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 300, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     assert seen & {8, 16, 32}, seen
 
 
@@ -849,8 +841,8 @@ def test_pregather_heavy_rows_and_mega_hubs_bitwise(mega):
     eng.set_option("pack_every", 4)
     eng.run(60)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 60, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 @pytest.mark.parametrize("multi", [1, 0, "mid0", "nolag", "iso0", "short0", "short_nolag", "trnt0", "bpx3"])
@@ -888,8 +880,8 @@ def test_pregather_multi_row_chains_bitwise(multi, ht, mega):
     eng.set_targets(tgt)
     tr = eng.run(45, err_every=1)
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 45, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     assert np.max(np.abs(a_ref - tgt)) == tr[-1]
 
 
@@ -905,8 +897,8 @@ def test_pregather_degree_layout_hub_buckets_first(mega):
     assert eng.info()["mega_hubs"] > 0
     eng.run(40)
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 40, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 @pytest.mark.parametrize("tile", [2048, 1024, 512])
@@ -922,8 +914,8 @@ def test_mega_hub_staged_chain_bitwise(tile, mega):
     eng.set_option("pack_every", 4)
     eng.run(60)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 60, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_star_hub_above_default_mega_threshold():
@@ -941,8 +933,8 @@ def test_star_hub_above_default_mega_threshold():
     eng = fu.CollectAll(g, v, kernel="recon")
     eng.run(40)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 40, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 @pytest.mark.parametrize("wave_heavy", [0, 1])
@@ -959,8 +951,8 @@ def test_heavy_rows_wave_and_block_paths_bitwise(tile, wave_heavy):
     eng.set_option("pack_every", 4)
     eng.run(80)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 80, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def test_round0_flows_sparse_rows_and_hubs():
@@ -979,8 +971,8 @@ def test_round0_flows_sparse_rows_and_hubs():
         for r in (1, 2, 3):
             eng.run(1)
             a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, r)
-            assert np.array_equal(eng.estimates(), a_ref), (kernel, r)
-            assert np.array_equal(eng.flows(), f_ref), (kernel, r)
+            assert_same_bits(eng.estimates(), a_ref, (kernel, r))
+            assert_same_bits(eng.flows(), f_ref, (kernel, r))
 
 
 def test_stage_layout_slices_and_unbuildable_graphs():
@@ -1027,8 +1019,8 @@ def test_rmat24_degree_layout_bitwise():
     a, f = eng.estimates(), eng.flows()
     eng.close()
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 20, nthreads=16)
-    assert np.array_equal(a, a_ref)
-    assert np.array_equal(f, f_ref)
+    assert_same_bits(a, a_ref)
+    assert_same_bits(f, f_ref)
     del a_ref, f_ref
     _check_flow_bookkeeping(g, v, a, f)
 
@@ -1046,8 +1038,8 @@ def test_rgg_2pow23_partition_unit_bitwise():
     d.run(20)
     g = fu.Graph.random_geometric(n, avg_deg=8.0, seed=1)
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 20, nthreads=16)
-    assert np.array_equal(d.estimates(), a_ref)
-    assert np.array_equal(d.flows(), f_ref)
+    assert_same_bits(d.estimates(), a_ref)
+    assert_same_bits(d.flows(), f_ref)
     d.close()
 
 
@@ -1104,8 +1096,8 @@ def test_rgg_2pow28_two_partitions_one_gpu_bitwise():
     print("[big] C oracle done", flush=True)
     stop.set()
     for lo, hi, a, f in got:
-        assert np.array_equal(a, a_ref[lo:hi])
-        assert np.array_equal(f, f_ref[rowptr[lo]:rowptr[hi]])
+        assert_same_bits(a, a_ref[lo:hi])
+        assert_same_bits(f, f_ref[rowptr[lo]:rowptr[hi]])
 
 
 @pytest.mark.timeout(900)
@@ -1132,15 +1124,15 @@ def test_rgg64m_single_gpu_properties():
     mass = (math.fsum(a.tolist()) + float(np.sum(f))) / n
     assert abs(mass - mean_v) < 1e-9 * mean_v
     a_ref, f_ref = coracle.ca_sync(g.rowptr, g.col, g.rev, v, 10, nthreads=16)
-    assert np.array_equal(a, a_ref)
-    assert np.array_equal(f, f_ref)
+    assert_same_bits(a, a_ref)
+    assert_same_bits(f, f_ref)
     del a, f
     part = RggPart(n, avg_deg=8.0, seed=1, nparts=1, part=0)
     d = DistCollectAll(part.to_plan(), part.values(seed=0), unique_id())
     d.run(20)
     coracle.ca_rounds(g.rowptr, g.col, g.rev, v, 10, a_ref, f_ref, nthreads=16)
-    assert np.array_equal(d.estimates(), a_ref)
-    assert np.array_equal(d.flows(), f_ref)
+    assert_same_bits(d.estimates(), a_ref)
+    assert_same_bits(d.flows(), f_ref)
     d.close()
 
 
@@ -1178,8 +1170,8 @@ def test_random_configurations_bitwise(seed):
         eng.run(k)
         rounds += k
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, rounds, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref), (fam, layout)
-    assert np.array_equal(eng.flows(), f_ref), (fam, layout)
+    assert_same_bits(eng.estimates(), a_ref, (fam, layout))
+    assert_same_bits(eng.flows(), f_ref, (fam, layout))
 
 
 @pytest.mark.parametrize("tile", [2048, 1024, 512])
@@ -1204,8 +1196,8 @@ def test_c16_narrow_and_wide_tiles_bitwise(tile):
         eng.set_option("tile_edges", tile)
         eng.set_option("c16", c16)
         eng.run(25)
-        assert np.array_equal(eng.estimates(), a_ref), c16
-        assert np.array_equal(eng.flows(), f_ref), c16
+        assert_same_bits(eng.estimates(), a_ref, c16)
+        assert_same_bits(eng.flows(), f_ref, c16)
         eng.close()
 
 
@@ -1268,8 +1260,8 @@ def test_lag_flows_every_round_and_switches():
     for r in range(1, 12):  # rounds 0 .. r-1 run: compare after each
         eng.run(1)
         a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, r, nthreads=16)
-        assert np.array_equal(eng.estimates(), a_ref), r
-        assert np.array_equal(eng.flows(), f_ref), r
+        assert_same_bits(eng.estimates(), a_ref, r)
+        assert_same_bits(eng.flows(), f_ref, r)
     eng.run(5)
     eng.set_option("mega_hub", 700)  # tiles and staging layout rebuilt: the lagged flows are written first
     eng.run(4)
@@ -1279,12 +1271,13 @@ def test_lag_flows_every_round_and_switches():
     eng.set_option("multi_mid", 0)  # the lagged set shrinks between two rounds of one parity
     eng.run(7)
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 11 + 5 + 4 + 3 + 7, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
     eng.reset()
     eng.run(9)
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 9, nthreads=16)
-    assert np.array_equal(eng.flows(), f_ref) and np.array_equal(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
+    assert_same_bits(eng.estimates(), a_ref)
 
 
 def test_lag_with_autotune_kernel_switches():
@@ -1299,32 +1292,8 @@ def test_lag_with_autotune_kernel_switches():
     eng.set_option("pack_every", 4)
     eng.run(200)
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 200, nthreads=16)
-    assert np.array_equal(eng.estimates(), a_ref)
-    assert np.array_equal(eng.flows(), f_ref)
-
-
-CLASS_EDGE_DEGREES = [0, 1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024,
-                      1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 12000]
-
-
-def _class_edge_graph(seed):
-    """Star centres of exactly the degrees above (each row class's first and last degree: heavy
-    rows at > 128, multi-row blocks at > 256, the register launch's 1024, the mega hubs at >
-    8192), their leaves drawn from a random background graph that never touches a centre."""
-    rng = np.random.default_rng(seed)
-    k, n_leaf = len(CLASS_EDGE_DEGREES), 16000
-    n = k + n_leaf
-    src, dst = [], []
-    for c, d in enumerate(CLASS_EDGE_DEGREES):
-        leaves = k + rng.choice(n_leaf, size=d, replace=False)
-        src.append(np.full(d, c))
-        dst.append(leaves)
-    m = 3 * n_leaf
-    src.append(k + rng.integers(0, n_leaf, m))
-    dst.append(k + rng.integers(0, n_leaf, m))
-    g = fu.Graph.from_edges(n, np.concatenate(src), np.concatenate(dst))
-    assert [int(x) for x in g.degrees[:k]] == CLASS_EDGE_DEGREES
-    return g
+    assert_same_bits(eng.estimates(), a_ref)
+    assert_same_bits(eng.flows(), f_ref)
 
 
 def _isolated_then_heavy_graph(tail):
@@ -1367,8 +1336,8 @@ def test_isolated_rows_before_heavy_rows_given_layout_bitwise(tail, opts):
         eng.run(k)
         done += k
         a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, done, nthreads=16)
-        assert np.array_equal(eng.estimates(), a_ref), done
-        assert np.array_equal(eng.flows(), f_ref), done
+        assert_same_bits(eng.estimates(), a_ref, done)
+        assert_same_bits(eng.flows(), f_ref, done)
     eng.close()
 
 
@@ -1393,5 +1362,5 @@ def test_row_class_boundaries_bitwise(kernel, opts, layout):
         eng.run(k)
         done += k
         a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, done, nthreads=16)
-        assert np.array_equal(eng.estimates(), a_ref), done
-        assert np.array_equal(eng.flows(), f_ref), done
+        assert_same_bits(eng.estimates(), a_ref, done)
+        assert_same_bits(eng.flows(), f_ref, done)
