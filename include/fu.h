@@ -210,6 +210,43 @@ int fu_destroy(fu_handle *h);
 int fu_copy_bandwidth(int32_t device, int64_t bytes, int32_t iters, double *gbs);
 
 /* ======================================================================================
+ * Batched collect-all engine: K value columns (1 <= K <= 16) over one graph, one pass per
+ * round. Each column is an independent scalar run of the engine above (the same arithmetic,
+ * bitwise equal to K separate handles): AVG, COUNT, SUM, moments and histogram bins of one
+ * network share the column indices, the row structure and one K-wide estimate gather per
+ * edge. value, target and estimates are node-major ([i * k + c]); flows are edge-major
+ * ([e * k + c]) in the caller's CSR order. The graph must be symmetric. Arguments are
+ * checked before any HIP call: k outside 1..16 is FU_ERR_ARG, an asymmetric graph
+ * FU_ERR_GRAPH, also on a host without a GPU. No options: one kernel, every degree.
+ * ==================================================================================== */
+typedef struct fu_batch fu_batch;
+
+/* rowptr[n+1], col[e], rev[e] (rev may be NULL: symmetry is checked natively), value[n*k]. */
+int fu_batch_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                    const int32_t *rev, int32_t k, const double *value, int32_t device,
+                    fu_batch **out);
+int fu_batch_create_from_graph(const fu_graph *g, int32_t k, const double *value,
+                               int32_t device, fu_batch **out);
+/* Zero the state: the next round run is round 0. */
+int fu_batch_reset(fu_batch *b);
+/* Run `rounds` rounds. If err_every > 0 (targets required), err_trace receives, after every
+ * err_every-th round, max_i |a[i][c] - target[i][c]| per column: (rounds / err_every) * k
+ * entries, round-major. A NaN in one column makes only that column's entries NaN.
+ * Asynchronous unless err_every > 0. */
+int fu_batch_run(fu_batch *b, int32_t rounds, int32_t err_every, double *err_trace);
+/* Same rounds, timed with HIP events on the handle's stream (synchronises). */
+int fu_batch_run_timed(fu_batch *b, int32_t rounds, float *ms);
+/* Per-node, per-column convergence targets, target[n*k]. */
+int fu_batch_set_targets(fu_batch *b, const double *target);
+/* out[k]: max_i |a[i][c] - target[i][c]| on the current estimates (synchronises). */
+int fu_batch_max_err(fu_batch *b, double *out);
+int fu_batch_get_estimates(fu_batch *b, double *a_out /* n*k */);
+int fu_batch_get_flows(fu_batch *b, double *f_out /* e*k */);
+int fu_batch_get_round(fu_batch *b, int64_t *rounds_done);
+int fu_batch_synchronize(fu_batch *b);
+int fu_batch_destroy(fu_batch *b);
+
+/* ======================================================================================
  * Tick-level replay (pairwise mode, and faithful collect-all on small platforms).
  * Replaces the SimGrid maestro + Peer.loop (CA:70-85 / PW:69-84): the loop's control flow
  * never depends on fp values, so the whole schedule is precomputed on the host as a trace.

@@ -78,6 +78,18 @@ _SIGS = {
     "fu_synchronize": ([vp], ctypes.c_int),
     "fu_destroy": ([vp], ctypes.c_int),
     "fu_copy_bandwidth": ([i32, i64, i32, P(f64)], ctypes.c_int),
+    "fu_batch_create": ([i32, i64, vp, vp, vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_batch_create_from_graph": ([vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_batch_reset": ([vp], ctypes.c_int),
+    "fu_batch_run": ([vp, i32, i32, vp], ctypes.c_int),
+    "fu_batch_run_timed": ([vp, i32, P(f32)], ctypes.c_int),
+    "fu_batch_set_targets": ([vp, vp], ctypes.c_int),
+    "fu_batch_max_err": ([vp, vp], ctypes.c_int),
+    "fu_batch_get_estimates": ([vp, vp], ctypes.c_int),
+    "fu_batch_get_flows": ([vp, vp], ctypes.c_int),
+    "fu_batch_get_round": ([vp, P(i64)], ctypes.c_int),
+    "fu_batch_synchronize": ([vp], ctypes.c_int),
+    "fu_batch_destroy": ([vp], ctypes.c_int),
     "fu_trace_build": ([i32, vp, vp, i32, i32, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_ex": ([i32, vp, vp, i32, i32, cp, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_routes": ([i32, vp, vp, i32, i32, cp, cp, vp, P(vp)], ctypes.c_int),

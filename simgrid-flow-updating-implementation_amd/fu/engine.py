@@ -3,6 +3,9 @@
 * `CollectAll`: generation-synchronous collect-all rounds on one GPU (fu_create /
   fu_run_collectall). One round = Peer.on_receive for every directed edge + Peer.avg_and_send
   for every node (flowupdating-collectall.py:93-128), as one data-parallel kernel.
+* `CollectAllBatch`: the same rounds for K value columns over one graph in one pass
+  (fu_batch_*): AVG, COUNT, SUM, moments and histogram bins share the graph reads and one
+  K-wide estimate gather per edge; each column is bit-equal to a `CollectAll` run.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
   PW:69-84, and the SimGrid mailboxes), built natively on the host and replayed on the
   GPU one tick per batch. Used by the pairwise mode and by faithful small-platform runs.
@@ -176,6 +179,106 @@ class CollectAll:
     def close(self):
         if getattr(self, "_h", None):
             L.lib.fu_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class CollectAllBatch:
+    """K value columns over one graph in one pass per round (fu_batch_*): each column is an
+    independent run of `CollectAll`, bit for bit. `values` has shape (n, K), 1 <= K <= 16.
+
+    >>> x = uniform_values(g.n, seed=0); one = np.zeros(g.n); one[0] = 1.0
+    >>> eng = CollectAllBatch(g, np.stack([x, one], axis=1)); eng.run(1000)
+    >>> avg, inv_n = eng.estimates()[0]; total = avg / inv_n    # AVG, COUNT = 1 / inv_n, SUM
+    """
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None,
+                 rev=None, device: int = 0):
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim != 2:
+            raise ValueError(f"values must have shape (n, K), got {v.shape}")
+        self.values = np.ascontiguousarray(v)
+        k = int(v.shape[1])
+        out = L.vp()
+        if graph is not None:
+            if v.shape[0] != graph.n:
+                raise ValueError("values.shape[0] != graph.n")
+            L.call("fu_batch_create_from_graph", graph._h, k, L.ptr(self.values), int(device),
+                   ctypes.byref(out))
+            self.n, self.E = graph.n, graph.E
+        else:
+            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+            c = np.ascontiguousarray(col, dtype=np.int32)
+            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
+            n = len(rp) - 1
+            if v.shape[0] != n:
+                raise ValueError("values.shape[0] != n")
+            L.call("fu_batch_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), k,
+                   L.ptr(self.values), int(device), ctypes.byref(out))
+            self.n, self.E = n, int(rp[-1])
+        self.K = k
+        self._h = out
+
+    def reset(self):
+        L.call("fu_batch_reset", self._h)
+
+    def set_targets(self, target):
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        if t.shape != (self.n, self.K):
+            raise ValueError(f"targets must have shape ({self.n}, {self.K}), got {t.shape}")
+        L.call("fu_batch_set_targets", self._h, L.ptr(t))
+
+    def run(self, rounds: int, err_every: int = 0):
+        """Run `rounds` rounds; with err_every > 0 returns the (rounds // err_every, K)
+        max-error trace, one row per check and one entry per column."""
+        if err_every > 0:
+            trace = np.empty((max(rounds // err_every, 1), self.K))
+            L.call("fu_batch_run", self._h, int(rounds), int(err_every), L.ptr(trace))
+            return trace[:rounds // err_every]
+        L.call("fu_batch_run", self._h, int(rounds), 0, None)
+        return None
+
+    def run_timed(self, rounds: int) -> float:
+        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
+        ms = L.f32()
+        L.call("fu_batch_run_timed", self._h, int(rounds), ctypes.byref(ms))
+        return float(ms.value)
+
+    def max_err(self) -> np.ndarray:
+        out = np.empty(self.K)
+        L.call("fu_batch_max_err", self._h, L.ptr(out))
+        return out
+
+    def estimates(self) -> np.ndarray:
+        a = np.empty((self.n, self.K))
+        L.call("fu_batch_get_estimates", self._h, L.ptr(a))
+        return a
+
+    def flows(self) -> np.ndarray:
+        f = np.empty((max(self.E, 1), self.K))
+        L.call("fu_batch_get_flows", self._h, L.ptr(f))
+        return f[:self.E]
+
+    @property
+    def rounds_done(self) -> int:
+        r = L.i64()
+        L.call("fu_batch_get_round", self._h, ctypes.byref(r))
+        return int(r.value)
+
+    def synchronize(self):
+        L.call("fu_batch_synchronize", self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib.fu_batch_destroy(self._h)
             self._h = None
 
     def __del__(self):
