@@ -358,8 +358,19 @@ int fu_replay_get(fu_replay *r, double *last_avg, double *flows, double *est);
 /* "persistent" = 1: one launch for all ticks in dataflow order (per-node event streams,
  * unique message slots tagged by a sentinel); 0 = one launch per tick (default). Same bits.
  * "persistent_reg" = 1 (default): in persistent mode, when every node's thread can be
- * resident and the degree is <= 16, each thread keeps its node's state in registers. */
+ * resident and the degree is <= 16, each thread keeps its node's state in registers.
+ * "persistent_blocks", tests: B >= 1 = the generic persistent kernel launches min(B, its
+ * occupancy-derived grid) blocks, so each thread owns several nodes; 0 = that grid
+ * (default). Before the first tick only (FU_ERR_STATE after); negative = FU_ERR_ARG. No
+ * effect on the register kernel. */
 int fu_replay_set_option(fu_replay *r, const char *key, int64_t value);
+/* Which path a handle runs (read-only; in persistent mode it builds the per-node event
+ * streams if they are not built yet, as "persistent" = 1 does):
+ * info[0] persistent mode on; info[1] the register kernel will be used; info[2] its row
+ * registers (8 or 16; 0 if not used); info[3] the trace holds collect-all fires; info[4]
+ * blocks of the generic persistent launch (0 before the streams are built); info[5] unique
+ * message slots (likewise); info[6] max union degree; info[7] current tick. */
+int fu_replay_get_info(fu_replay *r, int64_t info[8]);
 int fu_replay_destroy(fu_replay *r);
 
 /* ======================================================================================

@@ -3799,7 +3799,8 @@ struct fu_replay {
   double2 *msg = nullptr;
   // persistent mode (built on first use)
   int persistent = 0;
-  unsigned pers_blocks = 1;
+  unsigned pers_blocks = 1;     // generic persistent launch: the occupancy-derived grid
+  int64_t pers_blocks_req = 0;  // option "persistent_blocks" (tests): 0 = pers_blocks
   std::vector<int32_t> h_tasks, h_events, h_out_ids;
   long long *node_off = nullptr, *cursor = nullptr;
   int4 *node_ev = nullptr;
@@ -3825,6 +3826,12 @@ using ReplayRegKernel = void (*)(int, int, const long long *, const int2 *, cons
 static ReplayRegKernel replay_reg_kernel(const fu_replay *r) {
   if (r->max_deg <= 8) return r->has_ca ? k_replay_persist_reg<8, true> : k_replay_persist_reg<8, false>;
   return r->has_ca ? k_replay_persist_reg<16, true> : k_replay_persist_reg<16, false>;
+}
+
+// Blocks of the generic persistent launch. "persistent_blocks" can only lower the grid
+// (fewer threads, more nodes each), never raise it above the resident bound.
+static unsigned replay_pers_blocks(const fu_replay *r) {
+  return r->pers_blocks_req > 0 ? (unsigned)std::min<int64_t>(r->pers_blocks, r->pers_blocks_req) : r->pers_blocks;
 }
 
 static int replay_build_persistent(fu_replay *r) {
@@ -3929,6 +3936,7 @@ int fu_replay_create(int32_t n, const int64_t *rowptr, const double *value, int3
     return fail(FU_ERR_ARG, "fu_replay_create: bad arguments");
   if (tick_task_off[0] != 0 || tick_task_off[ticks] != n_tasks) return fail(FU_ERR_ARG, "fu_replay_create: tick_task_off inconsistent");
   const int64_t E = rowptr[n];
+  bool has_ca = false;
   // validate the trace on the host: every index a kernel will dereference
   for (int64_t q = 0; q < n_tasks; ++q) {
     int32_t node = tasks[3 * q], b = tasks[3 * q + 1], e = tasks[3 * q + 2];
@@ -3942,6 +3950,7 @@ int fu_replay_create(int32_t n, const int64_t *rowptr, const double *value, int3
       else if (ev[0] == FU_EV_FIRE_PW) ok = ev[1] >= 0 && ev[1] < deg && ev[2] > ev[1] && ev[2] <= deg && ev[3] >= 0 && ev[3] < n_msgs;
       else ok = false;
       if (!ok) return fail(FU_ERR_ARG, "fu_replay_create: bad event " + std::to_string(p));
+      has_ca |= ev[0] == FU_EV_FIRE_CA;
     }
   }
   for (int64_t q = 0; q < n_out_ids; ++q)
@@ -3956,6 +3965,7 @@ int fu_replay_create(int32_t n, const int64_t *rowptr, const double *value, int3
   r->ticks = ticks;
   r->E = E;
   r->n_msgs = n_msgs;
+  r->has_ca = has_ca;
   for (int32_t i = 0; i < n; ++i) r->max_deg = std::max<int64_t>(r->max_deg, rowptr[i + 1] - rowptr[i]);
   r->h_tto.assign(tick_task_off, tick_task_off + ticks + 1);
   r->h_tasks.assign(tasks, tasks + 3 * n_tasks);
@@ -4023,7 +4033,7 @@ static int replay_ticks(fu_replay *r, int32_t tick_end, int32_t n_snap, const in
                          r->flow, r->est, r->last, r->pay, r->cursor, r->scur, n_snap, d_st, snaps_dev, r->status,
                          (long long)1 << 22);
     else
-      hipLaunchKernelGGL(k_replay_persist, dim3(r->pers_blocks), dim3(kBlock), 0, r->stream, r->n, tick_end,
+      hipLaunchKernelGGL(k_replay_persist, dim3(replay_pers_blocks(r)), dim3(kBlock), 0, r->stream, r->n, tick_end,
                          r->node_off, r->node_ev, r->node_tick, r->out_uid, r->rowptr, r->v, r->flow,
                          r->est, r->last, r->pay, r->cursor, r->scur, n_snap, d_st, snaps_dev, r->status,
                          (long long)1 << 22);
@@ -4119,7 +4129,33 @@ int fu_replay_set_option(fu_replay *r, const char *key, int64_t value) {
     r->pers_reg = value != 0;
     return FU_OK;
   }
+  if (!std::strcmp(key, "persistent_blocks")) {  // tests: blocks of the generic persistent launch
+    if (value < 0) return fail(FU_ERR_ARG, "fu_replay_set_option: persistent_blocks must be >= 0");
+    if (r->cur_tick != 0) return fail(FU_ERR_STATE, "fu_replay_set_option: persistent_blocks must be set before the first tick");
+    r->pers_blocks_req = value;
+    return FU_OK;
+  }
   return fail(FU_ERR_ARG, std::string("fu_replay_set_option: unknown key '") + key + "'");
+  FU_TRY_END
+}
+
+int fu_replay_get_info(fu_replay *r, int64_t info[8]) {
+  FU_TRY_BEGIN
+  if (!r || !info) return fail(FU_ERR_ARG, "fu_replay_get_info: NULL argument");
+  if (r->persistent && !r->pers_ready) {
+    HIP_TRY(hipSetDevice(r->device));
+    if (int rc = replay_build_persistent(r)) return rc;
+  }
+  const bool reg = r->persistent && r->pers_ready && r->reg_ok && r->pers_reg;
+  info[0] = r->persistent;
+  info[1] = reg;
+  info[2] = reg ? (r->max_deg <= 8 ? 8 : 16) : 0;
+  info[3] = r->has_ca;
+  info[4] = r->pers_ready ? (int64_t)replay_pers_blocks(r) : 0;
+  info[5] = r->pers_ready ? r->n_uid : 0;
+  info[6] = r->max_deg;
+  info[7] = r->cur_tick;
+  return FU_OK;
   FU_TRY_END
 }
 

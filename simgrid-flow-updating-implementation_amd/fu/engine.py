@@ -431,6 +431,17 @@ class Replay:
         L.call("fu_replay_get", self._h, L.ptr(last), L.ptr(fl), L.ptr(es))
         return last, fl[:self.E], es[:self.E]
 
+    def set_option(self, key: str, value: int):
+        L.call("fu_replay_set_option", self._h, key.encode(), int(value))
+
+    def info(self) -> list[int]:
+        """fu_replay_get_info: [persistent, register kernel used, its row registers (8 / 16 /
+        0), collect-all fires in the trace, blocks of the generic persistent launch, unique
+        message slots, max union degree, current tick]."""
+        info = np.zeros(8, dtype=np.int64)
+        L.call("fu_replay_get_info", self._h, L.ptr(info))
+        return [int(x) for x in info]
+
     def close(self):
         if getattr(self, "_h", None):
             L.lib.fu_replay_destroy(self._h)
