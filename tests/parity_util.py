@@ -6,6 +6,9 @@ bit for bit wherever that float is not a NaN (the signs of zeros and infinities 
 subnormal included), and is a NaN exactly where the reference's is a NaN. A NaN's sign and
 payload are not part of it: x86 generates 0xfff8000000000000, gfx950 0x7ff8000000000000,
 and Python prints both as `nan`."""
+import functools
+import math
+
 import numpy as np
 
 import fu
@@ -114,3 +117,82 @@ FAMILIES = {"neg": _neg, "sym": _sym, "wide": _wide, "ints": _ints, "binade": _b
 def count_neg_zero(x):
     """How many elements are -0.0 (bit pattern 0x8000000000000000)."""
     return int(np.count_nonzero(np.ascontiguousarray(x).view(np.uint64) == np.uint64(1 << 63)))
+
+
+@functools.lru_cache(maxsize=None)
+def _width_graph():
+    """ER(20000, 80000): the graph of the batched engine's width cases and of its K = 16 error
+    reduction case."""
+    return fu.Graph.erdos_renyi(20_000, 80_000, seed=1)
+
+
+def _isolated_then_heavy_rows(tail):
+    """(n, n_leaf, first isolated row, isolated rows, heavy row, mega hub) of the graph below."""
+    n_leaf, n_iso = 12000, 700
+    if tail == "heavy_hub":
+        iso0, heavy, hub = n_leaf, n_leaf + n_iso, n_leaf + n_iso + 1
+    elif tail == "hub_iso_heavy":
+        hub, iso0, heavy = n_leaf, n_leaf + 1, n_leaf + 1 + n_iso
+    else:
+        heavy, hub, iso0 = n_leaf, n_leaf + 1, n_leaf + 2
+    return n_leaf + n_iso + 2, n_leaf, iso0, n_iso, heavy, hub
+
+
+def _isolated_then_heavy_graph(tail):
+    """Layout "given" with runs of isolated rows right before a heavy row and a mega hub:
+    tail = "heavy_hub" puts [..., isolated x 700, heavy (300 edges), mega hub (9000 edges)] at
+    the end, "hub_iso_heavy" [..., mega hub, isolated x 700, heavy], "iso_end" keeps the
+    isolated run last (the k_isolated case)."""
+    rng = np.random.default_rng(21)
+    n, n_leaf, iso0, n_iso, heavy, hub = _isolated_then_heavy_rows(tail)
+    base = rng.integers(0, n_leaf, size=(3 * n_leaf, 2))
+    src, dst = [base[:, 0]], [base[:, 1]]
+    src += [np.full(300, heavy), np.full(9000, hub)]
+    dst += [rng.choice(n_leaf, 300, replace=False), rng.choice(n_leaf, 9000, replace=False)]
+    g = fu.Graph.from_edges(n, np.concatenate(src), np.concatenate(dst))
+    deg = g.degrees
+    assert deg[heavy] == 300 and deg[hub] == 9000 and not deg[iso0:iso0 + n_iso].any()
+    return g
+
+
+# ------------------------------------------------------------------------------------
+# planted targets: the error reduction (max_i |a_i - target_i|) with a chosen argmax
+# ------------------------------------------------------------------------------------
+# With component means as targets nothing controls which node holds the maximum, so a launch
+# that drops its rows' contribution (or adds a spurious one) stays unseen whenever the
+# maximum sits in another row class. Here the targets are the oracle's own last estimates,
+# a_{R-1}, except at one probe node p, where D is added: at every round r < R node p alone
+# holds the maximum, the expected entry np.max(np.abs(a_r - t)) is an exact IEEE subtraction
+# and fabs on the oracle's doubles, and the runner-up says what a dropped contribution would
+# have left.
+def planted_D(a_rounds, shift=0):
+    """The smallest power of two >= 4 max_{r,i} |a_r[i] - a_{R-1}[i]|, times 2^shift (shift
+    tells apart the probes that are planted at once: ranks, columns). The factor 4 is
+    headroom; the condition itself is planted_targets' assertion."""
+    a_rounds = np.asarray(a_rounds)
+    dev = float(np.max(np.abs(a_rounds - a_rounds[-1])))
+    assert np.isfinite(dev) and dev > 0.0, dev
+    m, e = math.frexp(4.0 * dev)  # 4 dev = m 2^e, 0.5 <= m < 1
+    return math.ldexp(1.0, (e - 1 if m == 0.5 else e) + shift)
+
+
+def planted_targets(a_rounds, p, D):
+    """a_rounds: (R, n) oracle estimates of rounds 0 .. R-1. Returns (t, want_trace,
+    runner_up): t = a_{R-1} with D added at node p; want_trace[r] = max_i |a_r[i] - t[i]|;
+    runner_up[r] = the same maximum over i != p, which is what the entry collapses to when
+    the launch that owns p drops its contribution. Asserts that at every round the maximum
+    is attained at p only (runner_up[r] < |a_r[p] - t[p]|)."""
+    a_rounds = np.asarray(a_rounds, dtype=np.float64)
+    assert a_rounds.ndim == 2 and 0 <= p < a_rounds.shape[1]
+    t = a_rounds[-1].copy()
+    t[p] = t[p] + D
+    err = np.abs(a_rounds - t)
+    at_p = err[:, p].copy()
+    err[:, p] = 0.0
+    runner_up = err.max(axis=1)
+    bad = ~(runner_up < at_p)
+    if bad.any():
+        r = int(np.argmax(bad))
+        raise AssertionError(f"probe {p}, D = {D!r}: at round {r} the probe's error {at_p[r]!r} does not exceed "
+                             f"the runner-up {runner_up[r]!r} at node {int(np.argmax(err[r]))}")
+    return t, np.maximum(at_p, runner_up), runner_up

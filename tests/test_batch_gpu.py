@@ -14,7 +14,7 @@ import coracle
 import fu
 import oracle
 from conftest import ca_sync_fixtures, load_npz
-from parity_util import FAMILIES, _class_edge_graph, assert_same_bits, count_neg_zero
+from parity_util import FAMILIES, _class_edge_graph, _width_graph, assert_same_bits, count_neg_zero
 
 pytestmark = pytest.mark.gpu
 
@@ -126,11 +126,6 @@ def test_row_classes_eight_value_families_side_by_side():
 # 3. widths
 # ------------------------------------------------------------------------------------
 WIDTH_ROUNDS = 40
-
-
-@functools.lru_cache(maxsize=None)
-def _width_graph():
-    return fu.Graph.erdos_renyi(20_000, 80_000, seed=1)
 
 
 @functools.lru_cache(maxsize=None)

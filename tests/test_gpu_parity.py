@@ -13,7 +13,8 @@ import coracle
 import fu
 from conftest import (ca_sync_fixtures, fixture_decl_csr, load_json, load_npz, tick_fixtures,
                       write_deployment_xml, write_platform_xml)
-from parity_util import _class_edge_graph, _er_with_outlier_pairs, assert_same_bits
+from parity_util import (_class_edge_graph, _er_with_outlier_pairs, _isolated_then_heavy_graph,
+                         assert_same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -1294,30 +1295,6 @@ def test_lag_with_autotune_kernel_switches():
     a_ref, f_ref = coracle.ca_sync(*g.arrays(), v, 200, nthreads=16)
     assert_same_bits(eng.estimates(), a_ref)
     assert_same_bits(eng.flows(), f_ref)
-
-
-def _isolated_then_heavy_graph(tail):
-    """Layout "given" with runs of isolated rows right before a heavy row and a mega hub:
-    tail = "heavy_hub" puts [..., isolated x 700, heavy (300 edges), mega hub (9000 edges)] at
-    the end, "hub_iso_heavy" [..., mega hub, isolated x 700, heavy], "iso_end" keeps the
-    isolated run last (the k_isolated case)."""
-    rng = np.random.default_rng(21)
-    n_leaf, n_iso = 12000, 700
-    base = rng.integers(0, n_leaf, size=(3 * n_leaf, 2))
-    src, dst = [base[:, 0]], [base[:, 1]]
-    if tail == "heavy_hub":
-        iso0, heavy, hub = n_leaf, n_leaf + n_iso, n_leaf + n_iso + 1
-    elif tail == "hub_iso_heavy":
-        hub, iso0, heavy = n_leaf, n_leaf + 1, n_leaf + 1 + n_iso
-    else:
-        heavy, hub, iso0 = n_leaf, n_leaf + 1, n_leaf + 2
-    n = n_leaf + n_iso + 2
-    src += [np.full(300, heavy), np.full(9000, hub)]
-    dst += [rng.choice(n_leaf, 300, replace=False), rng.choice(n_leaf, 9000, replace=False)]
-    g = fu.Graph.from_edges(n, np.concatenate(src), np.concatenate(dst))
-    deg = g.degrees
-    assert deg[heavy] == 300 and deg[hub] == 9000 and not deg[iso0:iso0 + n_iso].any()
-    return g
 
 
 @pytest.mark.parametrize("tail", ["heavy_hub", "hub_iso_heavy", "iso_end"])
