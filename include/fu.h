@@ -247,6 +247,58 @@ int fu_batch_synchronize(fu_batch *b);
 int fu_batch_destroy(fu_batch *b);
 
 /* ======================================================================================
+ * Lossy collect-all engine: the synchronous round of the engine above with a loss model.
+ * In round r >= 1, slot k = (i -> j) of row i either received the message j -> i of round
+ * r - 1 (F = -f[rev k], E = a[j]; CA:98-99) or lost it, and node i fires on the pair it
+ * stored itself (F = f[k], E = a[i]; CA:87-91, CA:117-119). Then, as everywhere,
+ * S = 0.0 + F.., T = 0.0 + E.. in row order, a = ((v - S) + T) / (deg + 1), f = (F + a) - E.
+ * Slot k of round r is lost iff down[k] != 0 or
+ *   u01(splitmix64_at(splitmix64_at(seed, r), k)) < p
+ * (the counter streams of fu_values_uniform; k = the caller's slot index, r = rounds since the
+ * last reset): a pure function of (seed, r, k, p), so run(17) equals run(5); run(12), and
+ * fu_lossy_delivered restates it on the host. p = 0 with no mask is bit-equal to
+ * fu_run_collectall; p = 1 loses everything. Round 0 delivers nothing. The reverse flow is
+ * gathered through rev (the flow reconstruction of the other engines needs every message to
+ * arrive). Arguments are checked before any HIP call, also on a host without a GPU.
+ * ==================================================================================== */
+typedef struct fu_lossy fu_lossy;
+
+/* rowptr[n+1], col[e], rev[e] (rev may be NULL: built natively), value[n]. A caller's rev is
+ * validated (in range, rev[rev[k]] == k, col[rev[k]] == row of k): FU_ERR_GRAPH otherwise,
+ * as for an asymmetric graph. */
+int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                    const int32_t *rev, const double *value, int32_t device, fu_lossy **out);
+int fu_lossy_create_from_graph(const fu_graph *g, const double *value, int32_t device,
+                               fu_lossy **out);
+/* Loss probability and seed of the rounds run after the call (defaults 0, 0). p outside
+ * [0, 1] or NaN: FU_ERR_ARG. */
+int fu_lossy_set_loss(fu_lossy *h, double p, uint64_t seed);
+/* down[e]: a non-zero byte loses slot k in every round run after the call (a link outage sets
+ * both directions; both ends keep the neighbour). NULL clears the mask (the default). */
+int fu_lossy_set_link_mask(fu_lossy *h, const uint8_t *down);
+/* The inputs change (value[n]); flows, estimates and the round counter are kept. */
+int fu_lossy_set_values(fu_lossy *h, const double *value);
+/* Zero the state, the round counter and the statistics. Loss, mask and values are kept. */
+int fu_lossy_reset(fu_lossy *h);
+/* As fu_batch_run with k = 1: rounds / err_every entries of max_i |a_i - target_i|. */
+int fu_lossy_run(fu_lossy *h, int32_t rounds, int32_t err_every, double *err_trace);
+int fu_lossy_run_timed(fu_lossy *h, int32_t rounds, float *ms);
+int fu_lossy_set_targets(fu_lossy *h, const double *target);
+int fu_lossy_max_err(fu_lossy *h, double *out);
+int fu_lossy_get_estimates(fu_lossy *h, double *a_out /* n */);
+int fu_lossy_get_flows(fu_lossy *h, double *f_out /* e */);
+int fu_lossy_get_round(fu_lossy *h, int64_t *rounds_done);
+/* out[0] = messages offered since the last reset (e per round >= 1), out[1] = how many of
+ * them were lost (loss probability or mask). Synchronises. */
+int fu_lossy_get_stats(fu_lossy *h, int64_t out[2]);
+int fu_lossy_synchronize(fu_lossy *h);
+int fu_lossy_destroy(fu_lossy *h);
+/* Host only, no GPU: out[q] = 1 if slot first + q is delivered in round `round` under
+ * (p, seed) with no mask, else 0 (round 0 delivers nothing). */
+int fu_lossy_delivered(uint64_t seed, int64_t round, int64_t first, int64_t count, double p,
+                       uint8_t *out);
+
+/* ======================================================================================
  * Tick-level replay (pairwise mode, and faithful collect-all on small platforms).
  * Replaces the SimGrid maestro + Peer.loop (CA:70-85 / PW:69-84): the loop's control flow
  * never depends on fp values, so the whole schedule is precomputed on the host as a trace.

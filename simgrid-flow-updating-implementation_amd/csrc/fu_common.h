@@ -16,19 +16,26 @@ int fail(int code, const std::string &msg);
 
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 
-inline uint64_t mix64(uint64_t z) {
+// The hash helpers also run in kernels (fu_lossy.hip): one definition for host and device.
+#if defined(__HIPCC__)
+#define FU_HD __host__ __device__
+#else
+#define FU_HD
+#endif
+
+FU_HD inline uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
 // Element i of the SplitMix64 stream seeded with `seed` (counter form, thread-count free).
-inline uint64_t splitmix_at(uint64_t seed, uint64_t i) { return mix64(seed + (i + 1) * kGolden); }
+FU_HD inline uint64_t splitmix_at(uint64_t seed, uint64_t i) { return mix64(seed + (i + 1) * kGolden); }
 // Sequential SplitMix64 step (same as the Python oracle's splitmix64()).
 inline uint64_t splitmix_next(uint64_t &state) {
   state += kGolden;
   return mix64(state);
 }
-inline double u01(uint64_t x) { return (double)(x >> 11) * 0x1.0p-53; }
+FU_HD inline double u01(uint64_t x) { return (double)(x >> 11) * 0x1.0p-53; }
 
 }  // namespace fu
 

@@ -6,6 +6,8 @@
 * `CollectAllBatch`: the same rounds for K value columns over one graph in one pass
   (fu_batch_*): AVG, COUNT, SUM, moments and histogram bins share the graph reads and one
   K-wide estimate gather per edge; each column is bit-equal to a `CollectAll` run.
+* `CollectAllLossy`: the same rounds with a loss model (fu_lossy_*): a lost message makes the
+  receiver fire on its own stored flow and estimate; the reverse flow is gathered through rev.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
   PW:69-84, and the SimGrid mailboxes), built natively on the host and replayed on the
   GPU one tick per batch. Used by the pairwise mode and by faithful small-platform runs.
@@ -279,6 +281,144 @@ class CollectAllBatch:
     def close(self):
         if getattr(self, "_h", None):
             L.lib.fu_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def lossy_delivered(seed: int, round: int, first: int, count: int, p: float) -> np.ndarray:
+    """uint8[count]: 1 where slot first + q is delivered in round `round` under (p, seed), the
+    decision of `CollectAllLossy` restated on the host (fu_lossy_delivered; no GPU)."""
+    out = np.empty(max(int(count), 1), dtype=np.uint8)
+    L.call("fu_lossy_delivered", int(seed), int(round), int(first), int(count), float(p), L.ptr(out))
+    return out[:int(count)]
+
+
+class CollectAllLossy:
+    """Synchronous collect-all rounds under message loss (fu_lossy_*): in every round >= 1 each
+    message is lost with probability `loss` (a pure function of seed, round and slot) or by a
+    link mask; the receiver then fires on the flow and estimate it stored itself (CA:87-91,
+    CA:117-119). loss = 0 with no mask is `CollectAll`, bit for bit.
+
+    >>> eng = CollectAllLossy(g, uniform_values(g.n, seed=0), loss=0.1, seed=7)
+    >>> eng.run(200); est = eng.estimates(); offered, lost = eng.stats
+    """
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
+                 loss: float = 0.0, seed: int = 0, device: int = 0):
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim != 1:
+            raise ValueError(f"values must have shape (n,), got {v.shape}")
+        self.values = np.ascontiguousarray(v)
+        out = L.vp()
+        if graph is not None:
+            if len(v) != graph.n:
+                raise ValueError("len(values) != graph.n")
+            L.call("fu_lossy_create_from_graph", graph._h, L.ptr(self.values), int(device), ctypes.byref(out))
+            self.n, self.E = graph.n, graph.E
+        else:
+            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+            c = np.ascontiguousarray(col, dtype=np.int32)
+            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
+            n = len(rp) - 1
+            if len(v) != n:
+                raise ValueError("len(values) != n")
+            if r is not None and len(r) != len(c):
+                raise ValueError("len(rev) != len(col)")
+            L.call("fu_lossy_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), L.ptr(self.values),
+                   int(device), ctypes.byref(out))
+            self.n, self.E = n, int(rp[-1])
+        self._h = out
+        if loss != 0.0 or seed != 0:
+            self.set_loss(loss, seed)
+
+    def set_loss(self, loss: float, seed: int = 0):
+        """Loss probability in [0, 1] and seed of the rounds run from now on."""
+        L.call("fu_lossy_set_loss", self._h, float(loss), int(seed))
+
+    def set_link_mask(self, down):
+        """down: E bytes, non-zero = slot lost in every round from now on; None clears."""
+        if down is None:
+            L.call("fu_lossy_set_link_mask", self._h, None)
+            return
+        d = np.ascontiguousarray(down, dtype=np.uint8)
+        if d.shape != (self.E,):
+            raise ValueError(f"mask must have shape ({self.E},), got {d.shape}")
+        L.call("fu_lossy_set_link_mask", self._h, L.ptr(d) if self.E else None)
+
+    def set_values(self, values):
+        """New inputs; flows, estimates and the round counter are kept."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f"values must have shape ({self.n},), got {v.shape}")
+        L.call("fu_lossy_set_values", self._h, L.ptr(v))
+        self.values = v
+
+    def reset(self):
+        L.call("fu_lossy_reset", self._h)
+
+    def set_targets(self, target):
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        if t.shape != (self.n,):
+            raise ValueError(f"targets must have shape ({self.n},), got {t.shape}")
+        L.call("fu_lossy_set_targets", self._h, L.ptr(t))
+
+    def run(self, rounds: int, err_every: int = 0):
+        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
+        if err_every > 0:
+            trace = np.empty(max(rounds // err_every, 1))
+            L.call("fu_lossy_run", self._h, int(rounds), int(err_every), L.ptr(trace))
+            return trace[:rounds // err_every]
+        L.call("fu_lossy_run", self._h, int(rounds), 0, None)
+        return None
+
+    def run_timed(self, rounds: int) -> float:
+        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
+        ms = L.f32()
+        L.call("fu_lossy_run_timed", self._h, int(rounds), ctypes.byref(ms))
+        return float(ms.value)
+
+    def max_err(self) -> float:
+        out = L.f64()
+        L.call("fu_lossy_max_err", self._h, ctypes.byref(out))
+        return float(out.value)
+
+    def estimates(self) -> np.ndarray:
+        a = np.empty(self.n)
+        L.call("fu_lossy_get_estimates", self._h, L.ptr(a))
+        return a
+
+    def flows(self) -> np.ndarray:
+        f = np.empty(max(self.E, 1))
+        L.call("fu_lossy_get_flows", self._h, L.ptr(f))
+        return f[:self.E]
+
+    @property
+    def rounds_done(self) -> int:
+        r = L.i64()
+        L.call("fu_lossy_get_round", self._h, ctypes.byref(r))
+        return int(r.value)
+
+    @property
+    def stats(self) -> tuple:
+        """(messages offered, messages lost) since the last reset; synchronises."""
+        s = np.zeros(2, dtype=np.int64)
+        L.call("fu_lossy_get_stats", self._h, L.ptr(s))
+        return int(s[0]), int(s[1])
+
+    def synchronize(self):
+        L.call("fu_lossy_synchronize", self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib.fu_lossy_destroy(self._h)
             self._h = None
 
     def __del__(self):
