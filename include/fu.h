@@ -299,6 +299,79 @@ int fu_lossy_delivered(uint64_t seed, int64_t round, int64_t first, int64_t coun
                        uint8_t *out);
 
 /* ======================================================================================
+ * Synchronous pairwise engine: every round a matching of the graph is chosen on the device
+ * and each matched pair runs one full pairwise exchange. State: per directed slot k (the
+ * caller's CSR order) the flow f[k] and the cached estimate c[k], per node last[i] (last_avg,
+ * PW:107); all zero after create and after reset. The graph must be symmetric.
+ *
+ * The matching of round r (r = rounds since the last reset; round 0 is an ordinary round),
+ * with key = splitmix64_at(seed, r) and h_i = splitmix64_at(key, i) (the counter streams of
+ * fu_values_uniform): a node of degree 0 is idle; node i proposes iff h_i & 1, else it
+ * listens; a proposer picks slot p_i = (h_i >> 1) % deg_i (unsigned 64-bit) and with it
+ * j = col[rowptr[i] + p_i]; the proposal is valid iff j listens; a listener with valid
+ * proposals accepts the one with the smallest ((h_i >> 32) << 32) | i. The accepted i is the
+ * pair's initiator, s = p_i, t = rev[rowptr[i] + s] - rowptr[j]. A pure function of (seed, r,
+ * graph): it does not depend on the launch shape, run(17) equals run(5); run(12), and
+ * fu_pair_matching restates it on the host.
+ *
+ * The exchange of a pair (i, s, j, t), without contraction:
+ *   1. i fires on s (PW:102-117): S = 0.0 + f[row i].. in row order, x = v_i - S,
+ *      a = (c[s] + x) / 2.0, f[s] = (f[s] + a) - c[s], c[s] = a, last[i] = a; message (f[s], a).
+ *   2. j receives (PW:98-99): c[t] = A, f[t] = -F; then j fires on t as in 1 (S over the whole
+ *      row j with the new f[t]); last[j] is set; message (f[t], a_j).
+ *   3. i receives: c[s] = a_j, f[s] = -f[t]. Node i does NOT fire again.
+ * Step 3 is the one deviation from the reference: at PW:100 every receive answers with a fire,
+ * so the ping-pong between two peers never ends; here it stops after one answer. That leaves f
+ * antisymmetric on the pair, and in exact arithmetic both ends then hold (x_i + x_j) / 2: the
+ * mass is conserved and the run is gossip averaging over the matching. Rows of different
+ * pairs are disjoint, so a round updates the state in place.
+ * Arguments are checked before any HIP call, also on a host without a GPU.
+ * ==================================================================================== */
+typedef struct fu_pair fu_pair;
+
+/* rowptr[n+1], col[e], rev[e] (rev may be NULL: built natively), value[n]; n >= 1. A caller's
+ * rev is validated as by fu_lossy_create: FU_ERR_GRAPH otherwise, as for an asymmetric graph. */
+int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                   const int32_t *rev, const double *value, int32_t device, fu_pair **out);
+int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t device,
+                              fu_pair **out);
+/* Seed of the matchings of the rounds run after the call (default 0). */
+int fu_pair_set_seed(fu_pair *h, uint64_t seed);
+/* "match": how the device finds the matching, 0 = proposers push one 64-bit atomicMin per valid
+ * proposal (default), 1 = every listener hashes its own row. Same matching, same bits; the
+ * switch exists for the A/B of tools/bench_pair.py. Unknown key or value: FU_ERR_ARG. */
+int fu_pair_set_option(fu_pair *h, const char *key, int64_t value);
+/* The inputs change (value[n]); flows, caches, last averages and the round counter are kept. */
+int fu_pair_set_values(fu_pair *h, const double *value);
+/* Zero the state, the round counter and the statistics. Seed and values are kept. */
+int fu_pair_reset(fu_pair *h);
+/* Run `rounds` rounds. If err_every > 0 (targets required), err_trace receives, after every
+ * err_every-th round, max_i |last_i - target_i| (rounds / err_every entries; the maximum is
+ * taken over bit patterns, so one NaN makes the entry NaN). Asynchronous unless err_every > 0;
+ * nothing inside a run waits for the host. */
+int fu_pair_run(fu_pair *h, int32_t rounds, int32_t err_every, double *err_trace);
+/* Same rounds, timed with HIP events on the handle's stream (synchronises). */
+int fu_pair_run_timed(fu_pair *h, int32_t rounds, float *ms);
+int fu_pair_set_targets(fu_pair *h, const double *target /* n */);
+/* max_i |last_i - target_i| on the current state (synchronises). */
+int fu_pair_max_err(fu_pair *h, double *out);
+/* last[n]: every node's average at its last fire (0.0 for a node that has not fired). */
+int fu_pair_get_estimates(fu_pair *h, double *last_out /* n */);
+int fu_pair_get_flows(fu_pair *h, double *f_out /* e */);
+/* c[e]: the cached estimate of every slot. */
+int fu_pair_get_cache(fu_pair *h, double *c_out /* e */);
+int fu_pair_get_round(fu_pair *h, int64_t *rounds_done);
+/* out[0] = pairs exchanged since the last reset, out[1] = nodes that have never fired since
+ * then. Synchronises. */
+int fu_pair_get_stats(fu_pair *h, int64_t out[2]);
+int fu_pair_synchronize(fu_pair *h);
+int fu_pair_destroy(fu_pair *h);
+/* Host only, no GPU: the matching of round `round` under `seed`. mate[i] = i's partner or -1,
+ * initiator[i] = 1 for the proposer of a pair, else 0. */
+int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed,
+                     int64_t round, int32_t *mate /* n */, uint8_t *initiator /* n */);
+
+/* ======================================================================================
  * Tick-level replay (pairwise mode, and faithful collect-all on small platforms).
  * Replaces the SimGrid maestro + Peer.loop (CA:70-85 / PW:69-84): the loop's control flow
  * never depends on fp values, so the whole schedule is precomputed on the host as a trace.

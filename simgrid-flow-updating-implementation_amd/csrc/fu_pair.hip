@@ -1,0 +1,681 @@
+// libfu synchronous pairwise engine for MI355X (gfx950): every round a matching of the graph is
+// chosen on the device and each matched pair runs one full pairwise exchange. C ABI: the
+// fu_pair section of include/fu.h. DESIGN.md §4.17.
+//
+// The matching of round r (key = splitmix_at(seed, r), h_i = splitmix_at(key, i)):
+//   node i of degree > 0 proposes iff h_i & 1, over its slot p_i = (h_i >> 1) % deg_i, to
+//   j = col[rowptr[i] + p_i]; the proposal is valid iff j listens (h_j & 1 == 0); a listener
+//   accepts the valid proposal with the smallest ((h_i >> 32) << 32) | i. pair_proposal below is
+//   the one statement of that rule: the kernels and fu_pair_matching share it.
+//
+// The exchange of a pair (i, s, j, t), t = rev[rowptr[i] + s] - rowptr[j]:
+//   1. i fires on s (PW:102-117): S = 0.0 + f[row i].. in row order, a_i = (c[s] + (v_i - S)) / 2,
+//      F1 = (f[s] + a_i) - c[s], last[i] = a_i.
+//   2. j receives (PW:98-99): c[t] = a_i, f[t] = -F1; j fires on t: S over row j with the new
+//      f[t], a_j = (a_i + (v_j - S)) / 2, F2 = (-F1 + a_j) - a_i, last[j] = a_j.
+//   3. i receives: c[s] = a_j, f[s] = -F2, and does not fire again (the reference's ping-pong,
+//      PW:100, never ends).
+// What a pair leaves behind: f[s] = -F2, f[t] = F2, c[s] = c[t] = a_j, last[i] = a_i,
+// last[j] = a_j. Rows of different pairs are disjoint, so the update is in place.
+//
+// A round is kp_propose (one 64-bit atomicMin per valid proposal into the listener's word) or
+// kp_scan (every listener hashes its own row; no atomics), then kp_exchange (a block compacts
+// its matched listeners, 8 lanes per pair load both flow rows into LDS, one lane carries the
+// two chains), then kp_heavy for the pairs with a row above kLightDeg (one block per pair, the
+// rows in LDS chunks, thread 0 carrying). Nothing in a round waits for the host.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fu_common.h"
+
+using namespace fu;
+
+#define HIP_TRY(expr)                                                                     \
+  do {                                                                                    \
+    hipError_t _e = (expr);                                                               \
+    if (_e != hipSuccess)                                                                 \
+      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
+  } while (0)
+
+namespace {
+
+constexpr int kBlock = 256;                 // threads per block (4 waves of 64)
+constexpr int kGroup = 8;                   // kp_exchange: lanes that load one pair's rows
+constexpr int kGroups = kBlock / kGroup;    // pairs a block works on at once
+constexpr int kLightDeg = 64;               // a pair with a row above this degree goes to kp_heavy
+constexpr int kChunk = 1024;                // kp_heavy: flows staged in LDS per chunk
+constexpr int kHeavyBlocks = 1024;          // kp_heavy: at most this many blocks share the round's heavy pairs
+
+using u64 = unsigned long long;
+constexpr u64 kNone = ~0ull;  // a listener's word without a proposal (no key is all-ones: i < 2^31)
+
+static_assert(sizeof(u64) == sizeof(uint64_t), "the words are read as uint64_t on the host");
+
+// ---- the rule, for host and device -----------------------------------------------------
+FU_HD inline uint64_t round_key(uint64_t seed, uint64_t r) { return splitmix_at(seed, r); }
+FU_HD inline int64_t pair_slot(uint64_t h, int64_t deg) { return (int64_t)((h >> 1) % (uint64_t)deg); }
+// Does node i make a valid proposal in the round keyed `key`? If so j is the listener it
+// proposes to and pk its priority there.
+FU_HD inline bool pair_proposal(uint64_t key, int32_t i, const int64_t *rowptr, const int32_t *col, int32_t &j,
+                                uint64_t &pk) {
+  const uint64_t h = splitmix_at(key, (uint64_t)i);
+  if (!(h & 1)) return false;  // i listens
+  const int64_t b = rowptr[i], d = rowptr[i + 1] - b;
+  if (d == 0) return false;  // idle
+  j = col[b + pair_slot(h, d)];
+  if (splitmix_at(key, (uint64_t)j) & 1) return false;  // j proposes too
+  pk = ((h >> 32) << 32) | (uint64_t)(uint32_t)i;
+  return true;
+}
+
+struct RoundArgs {
+  int32_t n;
+  const int64_t *rowptr;
+  const int32_t *col, *rev;
+  const double *v;
+  double *f, *c, *last;
+  u64 *word;             // per node: the smallest proposal key of this round, or kNone
+  unsigned char *fired;  // per node: 1 once the node has fired
+  u64 *pairs;            // the handle's pair counter
+  int2 *heavy;           // (i, j) of this round's heavy pairs
+  unsigned *n_heavy;
+  int32_t heavy_cap;
+  uint64_t key;          // round_key(seed, r)
+};
+
+// One fire and the answer to it, from the two sums: what the pair writes back.
+struct Exchange {
+  double a_i, a_j, F2;
+};
+__device__ inline double fire_avg(double c, double v, double S) { return (c + (v - S)) / 2.0; }
+
+// ---- matching, form A: proposers push -----------------------------------------------------
+__global__ __launch_bounds__(kBlock) void kp_propose(RoundArgs A) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *A.n_heavy = 0;  // the list of the round before has been consumed
+  if (i >= A.n) return;
+  int32_t j;
+  uint64_t pk;
+  if (pair_proposal(A.key, (int32_t)i, A.rowptr, A.col, j, pk)) atomicMin(&A.word[j], (u64)pk);
+}
+
+// ---- matching, form B: listeners pull -------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void kp_scan(RoundArgs A) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j == 0) *A.n_heavy = 0;
+  if (j >= A.n) return;
+  if (splitmix_at(A.key, (uint64_t)j) & 1) return;
+  u64 best = kNone;
+  for (int64_t k = A.rowptr[j]; k < A.rowptr[j + 1]; ++k) {
+    int32_t to;
+    uint64_t pk;
+    if (pair_proposal(A.key, A.col[k], A.rowptr, A.col, to, pk) && to == (int32_t)j) best = pk < best ? (u64)pk : best;
+  }
+  if (best != kNone) A.word[j] = best;
+}
+
+// ---- the exchange ------------------------------------------------------------------------
+// Thread t of block b looks at node b * kBlock + t: a listener whose word holds a key is
+// matched with the key's low half, and writes the word back to kNone. The block compacts its
+// pairs (ballot, listener order) and works on kGroups of them at a time: the 8 lanes of a
+// group load the pair's two flow rows coalesced into the group's LDS rows, then lane 0 runs
+// both chains from LDS in row order.
+__global__ __launch_bounds__(kBlock) void kp_exchange(RoundArgs A) {
+  __shared__ int2 s_pair[kBlock];
+  __shared__ int s_cnt[kBlock / 64];
+  __shared__ double s_f[kGroups][2 * kLightDeg];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t node = (int64_t)blockIdx.x * kBlock + tid;
+  u64 word = kNone;
+  if (node < A.n) {
+    word = A.word[node];
+    if (word != kNone) A.word[node] = kNone;
+  }
+  const bool matched = word != kNone;
+  const u64 bal = __ballot(matched);
+  if (lane == 0) s_cnt[w] = __popcll(bal);
+  __syncthreads();
+  int base = 0, np = 0;
+  for (int q = 0; q < kBlock / 64; ++q) {
+    if (q < w) base += s_cnt[q];
+    np += s_cnt[q];
+  }
+  if (matched) s_pair[base + __popcll(bal & ((1ull << lane) - 1))] = make_int2((int)(uint32_t)word, (int)node);
+  __syncthreads();
+  const int g = tid / kGroup, l = tid % kGroup;
+  for (int q0 = 0; q0 < np; q0 += kGroups) {  // np is the same in every thread: the barriers are uniform
+    const int q = q0 + g;
+    bool light = false;
+    int i = 0, j = 0, di = 0, dj = 0, t = 0;
+    int64_t bi = 0, bj = 0, ks = 0;
+    double cs = 0.0, vi = 0.0, vj = 0.0;
+    if (q < np) {
+      i = s_pair[q].x;
+      j = s_pair[q].y;
+      bi = A.rowptr[i];
+      di = (int)(A.rowptr[i + 1] - bi);
+      bj = A.rowptr[j];
+      dj = (int)(A.rowptr[j + 1] - bj);
+      if (di > kLightDeg || dj > kLightDeg) {
+        if (l == 0) {
+          const unsigned slot = atomicAdd(A.n_heavy, 1u);
+          if ((int64_t)slot < A.heavy_cap) A.heavy[slot] = make_int2(i, j);  // always: a heavy row is in one pair
+        }
+      } else {
+        light = true;
+        ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+        for (int d = l; d < di; d += kGroup) s_f[g][d] = A.f[bi + d];
+        for (int d = l; d < dj; d += kGroup) s_f[g][kLightDeg + d] = A.f[bj + d];
+        if (l == 0) {
+          t = (int)(A.rev[ks] - bj);
+          cs = A.c[ks];
+          vi = A.v[i];
+          vj = A.v[j];
+        }
+      }
+    }
+    __syncthreads();
+    if (light && l == 0) {
+      const double *fi = s_f[g], *fj = s_f[g] + kLightDeg;
+      double S = 0.0;
+      for (int d = 0; d < di; ++d) S = S + fi[d];
+      const double a_i = fire_avg(cs, vi, S);
+      const double F1 = (fi[ks - bi] + a_i) - cs;
+      S = 0.0;
+      for (int d = 0; d < dj; ++d) S = S + (d == t ? -F1 : fj[d]);
+      const double a_j = fire_avg(a_i, vj, S);
+      const double F2 = (-F1 + a_j) - a_i;
+      A.f[ks] = -F2;
+      A.c[ks] = a_j;
+      A.f[bj + t] = F2;
+      A.c[bj + t] = a_j;
+      A.last[i] = a_i;
+      A.last[j] = a_j;
+      A.fired[i] = 1;
+      A.fired[j] = 1;
+    }
+    __syncthreads();
+  }
+  if (tid == 0 && np > 0) atomicAdd(A.pairs, (u64)np);
+}
+
+// Pairs with a row above kLightDeg: one block per pair, at most kHeavyBlocks blocks sharing the
+// list. All threads load a chunk of a row coalesced into LDS; thread 0 carries the sum through
+// the chunk in row order, from chunk to chunk, first over row i and then, with -F1 in slot t's
+// place, over row j.
+__global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
+  __shared__ double s_f[kChunk];
+  const int tid = threadIdx.x;
+  const unsigned listed = *A.n_heavy;
+  const unsigned cnt = (int64_t)listed < A.heavy_cap ? listed : (unsigned)A.heavy_cap;
+  for (unsigned q = blockIdx.x; q < cnt; q += gridDim.x) {
+    const int i = A.heavy[q].x, j = A.heavy[q].y;
+    const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
+    const int64_t bj = A.rowptr[j], dj = A.rowptr[j + 1] - bj;
+    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+    const int64_t kt = A.rev[ks];
+    double S = 0.0;
+    for (int64_t c0 = 0; c0 < di; c0 += kChunk) {
+      const int m = (int)(di - c0 < kChunk ? di - c0 : kChunk);
+      for (int d = tid; d < m; d += kBlock) s_f[d] = A.f[bi + c0 + d];
+      __syncthreads();
+      if (tid == 0)
+        for (int d = 0; d < m; ++d) S = S + s_f[d];
+      __syncthreads();
+    }
+    double a_i = 0.0, F1 = 0.0;
+    if (tid == 0) {
+      const double cs = A.c[ks];
+      a_i = fire_avg(cs, A.v[i], S);
+      F1 = (A.f[ks] + a_i) - cs;
+    }
+    S = 0.0;
+    for (int64_t c0 = 0; c0 < dj; c0 += kChunk) {
+      const int m = (int)(dj - c0 < kChunk ? dj - c0 : kChunk);
+      for (int d = tid; d < m; d += kBlock) s_f[d] = A.f[bj + c0 + d];
+      __syncthreads();
+      if (tid == 0) {
+        const int64_t t = kt - bj - c0;  // slot t's place in this chunk, if it is in it
+        for (int d = 0; d < m; ++d) S = S + (d == t ? -F1 : s_f[d]);
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const double a_j = fire_avg(a_i, A.v[j], S);
+      const double F2 = (-F1 + a_j) - a_i;
+      A.f[ks] = -F2;
+      A.c[ks] = a_j;
+      A.f[kt] = F2;
+      A.c[kt] = a_j;
+      A.last[i] = a_i;
+      A.last[j] = a_j;
+      A.fired[i] = 1;
+      A.fired[j] = 1;
+    }
+  }
+}
+
+// max_i |last_i - target_i| as a uint64 bit pattern, the rule of the other engines: non-negative
+// doubles order like their bits, and a NaN with its sign cleared is above +inf.
+__global__ __launch_bounds__(kBlock) void kp_max_err(int n, const double *__restrict__ a,
+                                                     const double *__restrict__ target, u64 *__restrict__ err) {
+  u64 m = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const u64 x = (u64)__double_as_longlong(fabs(a[i] - target[i]));
+    m = x > m ? x : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 y = __shfl_xor(m, off, 64);
+    m = m > y ? m : y;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
+}
+
+// How many nodes have never fired: one atomic per block that found some.
+__global__ __launch_bounds__(kBlock) void kp_count_unfired(int n, const unsigned char *__restrict__ fired,
+                                                           u64 *__restrict__ out) {
+  int cnt = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) cnt += fired[i] == 0;
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  __shared__ int s_w[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int q = 0; q < kBlock / 64; ++q) t += s_w[q];
+    if (t) atomicAdd(out, (u64)t);
+  }
+}
+
+}  // namespace
+
+struct fu_pair {
+  int device = 0;
+  int32_t n = 0;
+  int64_t E = 0;
+  int64_t round = 0;
+  uint64_t seed = 0;
+  int match = 0;  // 0: kp_propose, 1: kp_scan
+  bool has_target = false;
+  int32_t n_heavy_rows = 0;  // rows above kLightDeg: the bound on a round's heavy pairs
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int64_t *rowptr = nullptr;
+  int32_t *col = nullptr, *rev = nullptr;
+  double *v = nullptr, *target = nullptr, *f = nullptr, *c = nullptr, *last = nullptr;
+  u64 *word = nullptr;
+  unsigned char *fired = nullptr;
+  int2 *heavy = nullptr;
+  unsigned *n_heavy = nullptr;
+  u64 *stat = nullptr;  // [0] pairs exchanged, [1] scratch of kp_count_unfired
+  u64 *err = nullptr;
+  int64_t errcap = 0;
+};
+
+namespace {
+
+template <typename T>
+int dmalloc(T **p, int64_t count) {
+  if (hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
+    *p = nullptr;
+    return fail(FU_ERR_ALLOC, "fu_pair: hipMalloc failed");
+  }
+  return FU_OK;
+}
+
+int set_device(fu_pair *h) {
+  HIP_TRY(hipSetDevice(h->device));
+  return FU_OK;
+}
+
+int err_slots(fu_pair *h, int64_t count) {
+  if (count <= h->errcap) return FU_OK;
+  if (h->err) hipFree(h->err);
+  h->err = nullptr;
+  h->errcap = 0;
+  if (int rc = dmalloc(&h->err, count)) return rc;
+  h->errcap = count;
+  return FU_OK;
+}
+
+unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
+
+int launch_err(fu_pair *h, u64 *slot) {
+  hipLaunchKernelGGL(kp_max_err, dim3(std::min(1024u, node_grid(h))), dim3(kBlock), 0, h->stream, h->n, h->last,
+                     h->target, slot);
+  HIP_TRY(hipGetLastError());
+  return FU_OK;
+}
+
+// Zero state: flows, caches, last averages, fired flags, counters; every word without a proposal.
+int zero_state(fu_pair *h) {
+  const size_t e = (size_t)std::max<int64_t>(h->E, 1), n = (size_t)h->n;
+  HIP_TRY(hipMemsetAsync(h->f, 0, sizeof(double) * e, h->stream));
+  HIP_TRY(hipMemsetAsync(h->c, 0, sizeof(double) * e, h->stream));
+  HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->fired, 0, n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->word, 0xFF, sizeof(u64) * n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * 2, h->stream));
+  HIP_TRY(hipMemsetAsync(h->n_heavy, 0, sizeof(unsigned), h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->round = 0;
+  return FU_OK;
+}
+
+int launch_round(fu_pair *h) {
+  RoundArgs A;
+  A.n = h->n;
+  A.rowptr = h->rowptr;
+  A.col = h->col;
+  A.rev = h->rev;
+  A.v = h->v;
+  A.f = h->f;
+  A.c = h->c;
+  A.last = h->last;
+  A.word = h->word;
+  A.fired = h->fired;
+  A.pairs = h->stat;
+  A.heavy = h->heavy;
+  A.n_heavy = h->n_heavy;
+  A.heavy_cap = h->n_heavy_rows;
+  A.key = round_key(h->seed, (uint64_t)h->round);
+  if (h->E > 0) {  // without edges every node is idle
+    const dim3 grid(node_grid(h)), block(kBlock);
+    if (h->match == 0)
+      hipLaunchKernelGGL(kp_propose, grid, block, 0, h->stream, A);
+    else
+      hipLaunchKernelGGL(kp_scan, grid, block, 0, h->stream, A);
+    hipLaunchKernelGGL(kp_exchange, grid, block, 0, h->stream, A);
+    if (h->n_heavy_rows > 0)
+      hipLaunchKernelGGL(kp_heavy, dim3(std::min(h->n_heavy_rows, kHeavyBlocks)), block, 0, h->stream, A);
+    HIP_TRY(hipGetLastError());
+  }
+  h->round += 1;
+  return FU_OK;
+}
+
+int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col) {
+  const std::string w(who);
+  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, w + ": rowptr[0] must be 0 and rowptr[n] == e");
+  for (int32_t i = 0; i < n; ++i)
+    if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, w + ": rowptr not monotone");
+  for (int64_t q = 0; q < e; ++q)
+    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, w + ": col index out of range at edge " + std::to_string(q));
+  return FU_OK;
+}
+
+// rev must pair every slot with its reverse slot, as in fu_lossy_create: a rev that fails this
+// would be an out-of-bounds or wrong access on the device.
+int check_rev(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev) {
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int64_t r = rev[k];
+      if (r < 0 || r >= e || rev[r] != k || col[r] != i || r < rowptr[col[k]] || r >= rowptr[col[k] + 1])
+        return fail(FU_ERR_GRAPH, "fu_pair_create: rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
+                                      std::to_string(k));
+    }
+  return FU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fu_pair_destroy(fu_pair *h) {
+  if (!h) return fail(FU_ERR_ARG, "fu_pair_destroy: bad arguments");
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (void *p : {(void *)h->rowptr, (void *)h->col, (void *)h->rev, (void *)h->v, (void *)h->target, (void *)h->f,
+                  (void *)h->c, (void *)h->last, (void *)h->word, (void *)h->fired, (void *)h->heavy, (void *)h->n_heavy,
+                  (void *)h->stat, (void *)h->err})
+    if (p) (void)hipFree(p);
+  if (h->ev0) (void)hipEventDestroy(h->ev0);
+  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return FU_OK;
+}
+
+// Every check on the arguments comes before the first HIP call, so a host without a GPU
+// reports an asymmetric graph or a bad rev as such.
+int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                   const double *value, int32_t device, fu_pair **out) {
+  FU_TRY_BEGIN
+  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return fail(FU_ERR_ARG, "fu_pair_create: bad arguments");
+  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_pair_create: more than 2^31-1 directed edges (rev is int32)");
+  if (int rc = check_csr("fu_pair_create", n, e, rowptr, col)) return rc;
+  std::vector<int32_t> built;
+  if (e > 0 && !rev) {
+    fu_graph g;
+    g.n = n;
+    g.rowptr.assign(rowptr, rowptr + n + 1);
+    g.col.assign(col, col + e);
+    if (int rc = fu::build_rev(g)) return rc;
+    built.swap(g.rev);
+    rev = built.data();
+  }
+  if (e > 0)
+    if (int rc = check_rev(n, e, rowptr, col, rev)) return rc;
+  int32_t heavy_rows = 0;
+  for (int32_t i = 0; i < n; ++i) heavy_rows += rowptr[i + 1] - rowptr[i] > kLightDeg;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, "fu_pair_create: no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, "fu_pair_create: device out of range");
+  auto *h = new fu_pair();
+  h->device = device;
+  h->n = n;
+  h->E = e;
+  h->n_heavy_rows = heavy_rows;
+  auto cleanup = [&](int code) { fu_pair_destroy(h); return code; };
+  int rc = FU_OK;
+  if ((rc = set_device(h))) return cleanup(rc);
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: hipStreamCreate failed"));
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
+    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: hipEventCreate failed"));
+  if ((rc = dmalloc(&h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(&h->col, e)) || (rc = dmalloc(&h->rev, e)) ||
+      (rc = dmalloc(&h->v, n)) || (rc = dmalloc(&h->target, n)) || (rc = dmalloc(&h->f, e)) || (rc = dmalloc(&h->c, e)) ||
+      (rc = dmalloc(&h->last, n)) || (rc = dmalloc(&h->word, n)) || (rc = dmalloc(&h->fired, n)) ||
+      (rc = dmalloc(&h->heavy, heavy_rows)) || (rc = dmalloc(&h->n_heavy, 1)) || (rc = dmalloc(&h->stat, 2)) ||
+      (rc = err_slots(h, 1)))
+    return cleanup(rc);
+  if (hipMemcpy(h->rowptr, rowptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess ||
+      (e && hipMemcpy(h->col, col, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
+      (e && hipMemcpy(h->rev, rev, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(h->v, value, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
+    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: upload failed"));
+  if ((rc = zero_state(h))) return cleanup(rc);
+  *out = h;
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_pair **out) {
+  FU_TRY_BEGIN
+  if (!g || !value || !out) return fail(FU_ERR_ARG, "fu_pair_create_from_graph: bad arguments");
+  const int64_t E = g->rowptr[g->n];
+  if ((int64_t)g->rev.size() != E) return fail(FU_ERR_GRAPH, "fu_pair_create_from_graph: graph is not symmetric");
+  return fu_pair_create(g->n, E, g->rowptr.data(), g->col.data(), E ? g->rev.data() : nullptr, value, device, out);
+  FU_TRY_END
+}
+
+int fu_pair_set_seed(fu_pair *h, uint64_t seed) {
+  if (!h) return fail(FU_ERR_ARG, "fu_pair_set_seed: bad arguments");
+  h->seed = seed;  // a kernel argument of the rounds launched from now on
+  return FU_OK;
+}
+
+int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
+  if (!h || !key) return fail(FU_ERR_ARG, "fu_pair_set_option: bad arguments");
+  if (std::strcmp(key, "match") == 0 && (value == 0 || value == 1)) {
+    h->match = (int)value;
+    return FU_OK;
+  }
+  return fail(FU_ERR_ARG, std::string("fu_pair_set_option: unknown option or value: ") + key);
+}
+
+int fu_pair_set_values(fu_pair *h, const double *value) {
+  FU_TRY_BEGIN
+  if (!h || !value) return fail(FU_ERR_ARG, "fu_pair_set_values: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipMemcpyAsync(h->v, value, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_reset(fu_pair *h) {
+  if (!h) return fail(FU_ERR_ARG, "fu_pair_reset: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  return zero_state(h);
+}
+
+int fu_pair_set_targets(fu_pair *h, const double *target) {
+  FU_TRY_BEGIN
+  if (!h || !target) return fail(FU_ERR_ARG, "fu_pair_set_targets: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipMemcpyAsync(h->target, target, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->has_target = true;
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_run(fu_pair *h, int32_t rounds, int32_t err_every, double *err_trace) {
+  FU_TRY_BEGIN
+  if (!h || rounds < 0) return fail(FU_ERR_ARG, "fu_pair_run: bad arguments");
+  if (err_every > 0 && !h->has_target) return fail(FU_ERR_STATE, "fu_pair_run: err_every > 0 needs fu_pair_set_targets");
+  if (int rc = set_device(h)) return rc;
+  const int64_t nerr = err_every > 0 ? rounds / err_every : 0;
+  if (nerr > 0) {
+    if (int rc = err_slots(h, nerr)) return rc;
+    HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64) * (size_t)nerr, h->stream));
+  }
+  for (int32_t r = 0; r < rounds; ++r) {
+    if (int rc = launch_round(h)) return rc;
+    if (nerr > 0 && (r + 1) % err_every == 0)
+      if (int rc = launch_err(h, h->err + ((r + 1) / err_every - 1))) return rc;
+  }
+  if (nerr > 0) {
+    std::vector<u64> bits((size_t)nerr);
+    HIP_TRY(hipMemcpyAsync(bits.data(), h->err, sizeof(u64) * bits.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (err_trace) std::memcpy(err_trace, bits.data(), sizeof(double) * bits.size());
+  }
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_run_timed(fu_pair *h, int32_t rounds, float *ms) {
+  FU_TRY_BEGIN
+  if (!h || !ms || rounds < 0) return fail(FU_ERR_ARG, "fu_pair_run_timed: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipEventRecord(h->ev0, h->stream));
+  for (int32_t r = 0; r < rounds; ++r)
+    if (int rc = launch_round(h)) return rc;
+  HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  HIP_TRY(hipEventSynchronize(h->ev1));
+  HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_max_err(fu_pair *h, double *out) {
+  FU_TRY_BEGIN
+  if (!h || !out) return fail(FU_ERR_ARG, "fu_pair_max_err: bad arguments");
+  if (!h->has_target) return fail(FU_ERR_STATE, "fu_pair_max_err: call fu_pair_set_targets first");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64), h->stream));
+  if (int rc = launch_err(h, h->err)) return rc;
+  u64 bits = 0;
+  HIP_TRY(hipMemcpyAsync(&bits, h->err, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  std::memcpy(out, &bits, sizeof(double));
+  return FU_OK;
+  FU_TRY_END
+}
+
+static int download(fu_pair *h, void *dst, const void *src, size_t bytes) {
+  if (bytes == 0) return FU_OK;
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return FU_OK;
+}
+
+int fu_pair_get_estimates(fu_pair *h, double *last_out) {
+  if (!h || !last_out) return fail(FU_ERR_ARG, "fu_pair_get_estimates: bad arguments");
+  return download(h, last_out, h->last, sizeof(double) * (size_t)h->n);
+}
+
+int fu_pair_get_flows(fu_pair *h, double *f_out) {
+  if (!h || (!f_out && h->E)) return fail(FU_ERR_ARG, "fu_pair_get_flows: bad arguments");
+  return download(h, f_out, h->f, sizeof(double) * (size_t)h->E);
+}
+
+int fu_pair_get_cache(fu_pair *h, double *c_out) {
+  if (!h || (!c_out && h->E)) return fail(FU_ERR_ARG, "fu_pair_get_cache: bad arguments");
+  return download(h, c_out, h->c, sizeof(double) * (size_t)h->E);
+}
+
+int fu_pair_get_round(fu_pair *h, int64_t *rounds_done) {
+  if (!h || !rounds_done) return fail(FU_ERR_ARG, "fu_pair_get_round: bad arguments");
+  *rounds_done = h->round;
+  return FU_OK;
+}
+
+int fu_pair_get_stats(fu_pair *h, int64_t out[2]) {
+  FU_TRY_BEGIN
+  if (!h || !out) return fail(FU_ERR_ARG, "fu_pair_get_stats: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipMemsetAsync(h->stat + 1, 0, sizeof(u64), h->stream));
+  hipLaunchKernelGGL(kp_count_unfired, dim3(std::min(1024u, node_grid(h))), dim3(kBlock), 0, h->stream, h->n, h->fired,
+                     h->stat + 1);
+  HIP_TRY(hipGetLastError());
+  u64 s[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(s, h->stat, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  out[0] = (int64_t)s[0];
+  out[1] = (int64_t)s[1];
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_synchronize(fu_pair *h) {
+  if (!h) return fail(FU_ERR_ARG, "fu_pair_synchronize: bad arguments");
+  if (int rc = set_device(h)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return FU_OK;
+}
+
+int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed, int64_t round, int32_t *mate,
+                     uint8_t *initiator) {
+  FU_TRY_BEGIN
+  if (n <= 0 || !rowptr || round < 0 || !mate || !initiator || rowptr[0] != 0 || (rowptr[n] > 0 && !col))
+    return fail(FU_ERR_ARG, "fu_pair_matching: bad arguments");
+  if (int rc = check_csr("fu_pair_matching", n, rowptr[n], rowptr, col)) return rc;
+  const uint64_t key = round_key(seed, (uint64_t)round);
+  std::vector<uint64_t> word((size_t)n, (uint64_t)kNone);
+  for (int32_t i = 0; i < n; ++i) {
+    int32_t j;
+    uint64_t pk;
+    if (pair_proposal(key, i, rowptr, col, j, pk)) word[j] = std::min(word[j], pk);
+  }
+  std::fill(mate, mate + n, -1);
+  std::fill(initiator, initiator + n, (uint8_t)0);
+  for (int32_t j = 0; j < n; ++j)
+    if (word[j] != (uint64_t)kNone) {
+      const int32_t i = (int32_t)(uint32_t)word[j];
+      mate[i] = j;
+      mate[j] = i;
+      initiator[i] = 1;
+    }
+  return FU_OK;
+  FU_TRY_END
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
     python -m fu collectall --sync --rounds 200         # synchronous rounds (hot path)
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --loss 0.1 [--loss-seed 7]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
 
 Defaults mirror flowupdating-collectall.py:154,157 (./platforms/small_platform.xml,
 ./actors.xml, watcher 1000.0 / 10.0 at CA:162).
@@ -15,7 +16,7 @@ import argparse
 import sys
 import time
 
-from .engine import CollectAll, CollectAllLossy
+from .engine import CollectAll, CollectAllLossy, PairwiseSync
 from .graph import Graph, component_means, uniform_values
 from .sim import CollectAllPeer, Engine, run_reference_main
 
@@ -36,7 +37,24 @@ def main(argv=None):
     ap.add_argument("--kernel", default="auto")
     ap.add_argument("--loss", type=float, default=None, help="bench-graph: message loss probability (lossy engine)")
     ap.add_argument("--loss-seed", type=int, default=0)
+    ap.add_argument("--pairs", action="store_true", help="bench-graph: synchronous pairwise rounds (pair engine)")
+    ap.add_argument("--pair-seed", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.mode == "bench-graph" and a.pairs:
+        if a.loss is not None:
+            ap.error("--pairs and --loss are exclusive")
+        g = Graph.from_spec(a.spec, seed=a.seed)
+        v = uniform_values(g.n, seed=0)
+        eng = PairwiseSync(g, v, seed=a.pair_seed, device=a.device)
+        t0 = time.perf_counter()
+        ms = eng.run_timed(a.rounds)
+        wall = time.perf_counter() - t0
+        tgt, _ = component_means(g.rowptr, g.col, v)
+        eng.set_targets(tgt)
+        print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
+              f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
+              f"max_err={eng.max_err():.3e} pairs={eng.stats[0]}")
+        return 0
     if a.mode == "bench-graph" and a.loss is not None:
         g = Graph.from_spec(a.spec, seed=a.seed)
         v = uniform_values(g.n, seed=0)

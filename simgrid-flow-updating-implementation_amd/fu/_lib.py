@@ -107,6 +107,24 @@ _SIGS = {
     "fu_lossy_synchronize": ([vp], ctypes.c_int),
     "fu_lossy_destroy": ([vp], ctypes.c_int),
     "fu_lossy_delivered": ([u64, i64, i64, i64, f64, vp], ctypes.c_int),
+    "fu_pair_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_pair_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_pair_set_seed": ([vp, u64], ctypes.c_int),
+    "fu_pair_set_option": ([vp, cp, i64], ctypes.c_int),
+    "fu_pair_set_values": ([vp, vp], ctypes.c_int),
+    "fu_pair_reset": ([vp], ctypes.c_int),
+    "fu_pair_run": ([vp, i32, i32, vp], ctypes.c_int),
+    "fu_pair_run_timed": ([vp, i32, P(f32)], ctypes.c_int),
+    "fu_pair_set_targets": ([vp, vp], ctypes.c_int),
+    "fu_pair_max_err": ([vp, P(f64)], ctypes.c_int),
+    "fu_pair_get_estimates": ([vp, vp], ctypes.c_int),
+    "fu_pair_get_flows": ([vp, vp], ctypes.c_int),
+    "fu_pair_get_cache": ([vp, vp], ctypes.c_int),
+    "fu_pair_get_round": ([vp, P(i64)], ctypes.c_int),
+    "fu_pair_get_stats": ([vp, vp], ctypes.c_int),
+    "fu_pair_synchronize": ([vp], ctypes.c_int),
+    "fu_pair_destroy": ([vp], ctypes.c_int),
+    "fu_pair_matching": ([i32, vp, vp, u64, i64, vp, vp], ctypes.c_int),
     "fu_trace_build": ([i32, vp, vp, i32, i32, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_ex": ([i32, vp, vp, i32, i32, cp, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_routes": ([i32, vp, vp, i32, i32, cp, cp, vp, P(vp)], ctypes.c_int),

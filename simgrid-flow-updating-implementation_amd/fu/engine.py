@@ -8,6 +8,8 @@
   K-wide estimate gather per edge; each column is bit-equal to a `CollectAll` run.
 * `CollectAllLossy`: the same rounds with a loss model (fu_lossy_*): a lost message makes the
   receiver fire on its own stored flow and estimate; the reverse flow is gathered through rev.
+* `PairwiseSync`: synchronous pairwise rounds (fu_pair_*): a matching per round chosen on the
+  device, one full pairwise exchange per matched pair; `pair_matching` restates it on the host.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
   PW:69-84, and the SimGrid mailboxes), built natively on the host and replayed on the
   GPU one tick per batch. Used by the pairwise mode and by faithful small-platform runs.
@@ -419,6 +421,152 @@ class CollectAllLossy:
     def close(self):
         if getattr(self, "_h", None):
             L.lib.fu_lossy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def pair_matching(g, seed: int, r: int):
+    """(mate, initiator) of round r under `seed` on graph g (a Graph, or a (rowptr, col) pair):
+    mate[i] is i's partner or -1, initiator[i] is 1 for the proposer of a pair. The matching of
+    `PairwiseSync` restated on the host (fu_pair_matching; no GPU)."""
+    rowptr, col = (g.rowptr, g.col) if isinstance(g, Graph) else g
+    rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+    c = np.ascontiguousarray(col, dtype=np.int32)
+    n = len(rp) - 1
+    mate = np.empty(max(n, 1), dtype=np.int32)
+    init = np.empty(max(n, 1), dtype=np.uint8)
+    L.call("fu_pair_matching", n, L.ptr(rp), L.ptr(c) if len(c) else None, int(seed), int(r), L.ptr(mate), L.ptr(init))
+    return mate[:n], init[:n]
+
+
+class PairwiseSync:
+    """Synchronous pairwise rounds (fu_pair_*): every round a matching of the graph is chosen on
+    the device (a pure function of seed, round and graph) and each matched pair runs one full
+    pairwise exchange: the initiator fires (PW:102-117), the listener receives and fires back,
+    the initiator receives and stops there. Gossip averaging over the matching; no host-built
+    schedule, so million-node graphs and thousands of rounds are one run() call.
+
+    >>> eng = PairwiseSync(g, uniform_values(g.n, seed=0), seed=7)
+    >>> eng.run(1000); est = eng.estimates(); pairs, never_fired = eng.stats
+    """
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
+                 seed: int = 0, device: int = 0):
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim != 1:
+            raise ValueError(f"values must have shape (n,), got {v.shape}")
+        self.values = np.ascontiguousarray(v)
+        out = L.vp()
+        if graph is not None:
+            if len(v) != graph.n:
+                raise ValueError("len(values) != graph.n")
+            L.call("fu_pair_create_from_graph", graph._h, L.ptr(self.values), int(device), ctypes.byref(out))
+            self.n, self.E = graph.n, graph.E
+        else:
+            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+            c = np.ascontiguousarray(col, dtype=np.int32)
+            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
+            n = len(rp) - 1
+            if len(v) != n:
+                raise ValueError("len(values) != n")
+            if r is not None and len(r) != len(c):
+                raise ValueError("len(rev) != len(col)")
+            L.call("fu_pair_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), L.ptr(self.values),
+                   int(device), ctypes.byref(out))
+            self.n, self.E = n, int(rp[-1])
+        self._h = out
+        if seed != 0:
+            self.set_seed(seed)
+
+    def set_seed(self, seed: int):
+        """Seed of the matchings of the rounds run from now on."""
+        L.call("fu_pair_set_seed", self._h, int(seed))
+
+    def set_option(self, key: str, value: int):
+        """"match": 0 = proposers push (atomicMin, default), 1 = listeners scan their rows."""
+        L.call("fu_pair_set_option", self._h, key.encode(), int(value))
+
+    def set_values(self, values):
+        """New inputs; flows, caches, last averages and the round counter are kept."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.shape != (self.n,):
+            raise ValueError(f"values must have shape ({self.n},), got {v.shape}")
+        L.call("fu_pair_set_values", self._h, L.ptr(v))
+        self.values = v
+
+    def reset(self):
+        L.call("fu_pair_reset", self._h)
+
+    def set_targets(self, target):
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        if t.shape != (self.n,):
+            raise ValueError(f"targets must have shape ({self.n},), got {t.shape}")
+        L.call("fu_pair_set_targets", self._h, L.ptr(t))
+
+    def run(self, rounds: int, err_every: int = 0):
+        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
+        if err_every > 0:
+            trace = np.empty(max(rounds // err_every, 1))
+            L.call("fu_pair_run", self._h, int(rounds), int(err_every), L.ptr(trace))
+            return trace[:rounds // err_every]
+        L.call("fu_pair_run", self._h, int(rounds), 0, None)
+        return None
+
+    def run_timed(self, rounds: int) -> float:
+        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
+        ms = L.f32()
+        L.call("fu_pair_run_timed", self._h, int(rounds), ctypes.byref(ms))
+        return float(ms.value)
+
+    def max_err(self) -> float:
+        out = L.f64()
+        L.call("fu_pair_max_err", self._h, ctypes.byref(out))
+        return float(out.value)
+
+    def estimates(self) -> np.ndarray:
+        """Every node's average at its last fire (0.0 before its first)."""
+        a = np.empty(self.n)
+        L.call("fu_pair_get_estimates", self._h, L.ptr(a))
+        return a
+
+    def flows(self) -> np.ndarray:
+        f = np.empty(max(self.E, 1))
+        L.call("fu_pair_get_flows", self._h, L.ptr(f))
+        return f[:self.E]
+
+    def cache(self) -> np.ndarray:
+        """The cached estimate of every slot."""
+        c = np.empty(max(self.E, 1))
+        L.call("fu_pair_get_cache", self._h, L.ptr(c))
+        return c[:self.E]
+
+    @property
+    def rounds_done(self) -> int:
+        r = L.i64()
+        L.call("fu_pair_get_round", self._h, ctypes.byref(r))
+        return int(r.value)
+
+    @property
+    def stats(self) -> tuple:
+        """(pairs exchanged, nodes that have never fired) since the last reset; synchronises."""
+        s = np.zeros(2, dtype=np.int64)
+        L.call("fu_pair_get_stats", self._h, L.ptr(s))
+        return int(s[0]), int(s[1])
+
+    def synchronize(self):
+        L.call("fu_pair_synchronize", self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib.fu_pair_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,201 @@
+#!/usr/bin/env python3
+"""The synchronous pairwise engine (fu.PairwiseSync), in one process.
+
+1. RR(65536, 8), R rounds from zero: fu_pair beside fu_replay (per-tick batches and the
+   persistent kernel) on the host-built trace of the same 3 R ticks (a round is three ticks:
+   the initiators' FIRE_PW; the listeners' RECV and FIRE_PW; the initiators' RECV). Both carry
+   the same events; their final states are compared bit for bit before any number is printed.
+   One JSON line: us per round of each, pairwise updates/s (two fires per pair), trace size and
+   host build time, and ratio = t_pair / t_replay_persistent (below 0.85 a win, above 1.15 a
+   loss, a tie between).
+2. ER(n, 4 n) and RR(n, 8), n = 1,000,000: rounds 1 .. R-1 timed on the device, median of
+   --reps windows, each after a reset, for both forms of the matching ("match" 0: proposers
+   push an atomicMin, 1: listeners scan their rows). One JSON line per graph and form with
+   us_per_round, pairs_per_round, the byte model
+     bytes = sum over pairs of 8 (deg_i + deg_j) + 116
+   (both flow rows; reads of c[s], c[t], v_i, v_j, four row pointers, one rev; writes of two
+   flows, two caches, two last averages; the matching's own traffic is not in it), roofline =
+   bytes / 8 TB/s / time, and the box's copy rate.
+
+    python tools/bench_pair.py [--rounds 200] [--n 1000000] [--reps 7] [--skip-replay]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "simgrid-flow-updating-implementation_amd"))
+
+import numpy as np  # noqa: E402
+
+import fu  # noqa: E402
+from fu import _lib as L  # noqa: E402
+
+PEAK = 8.0e12  # bytes / s
+SEED = 7
+
+
+def round_pairs(g, src, seed, r):
+    """(i, s, j, t) arrays of round r from the host matching (fu_pair_matching); the slot is
+    where the partner sits in the initiator's row (simple graphs)."""
+    mate, ini = fu.pair_matching(g, seed, r)
+    ks = np.flatnonzero((ini[src] == 1) & (g.col == mate[src]))
+    i = src[ks]
+    j = g.col[ks].astype(np.int64)
+    return i, ks - g.rowptr[i], j, g.rev[ks] - g.rowptr[j]
+
+
+def build_trace(g, seed, rounds):
+    """The rounds as replay ticks (three per round), and the pairs of the run."""
+    src = np.repeat(np.arange(g.n, dtype=np.int64), np.diff(g.rowptr))
+    deg = np.diff(g.rowptr)
+    tasks, events, tto = [], [], [0]
+    q = nt = ne = 0
+    for r in range(rounds):
+        i, s, j, t = round_pairs(g, src, seed, r)
+        p = len(i)
+        m1 = 2 * (q + np.arange(p))
+        z = np.zeros(p, dtype=np.int64)
+        e1 = ne + np.arange(p)
+        e2 = ne + p + 2 * np.arange(p)
+        e3 = ne + 3 * p + np.arange(p)
+        tasks += [np.stack([i, e1, e1 + 1], 1), np.stack([j, e2, e2 + 2], 1), np.stack([i, e3, e3 + 1], 1)]
+        recv_fire = np.empty((2 * p, 4), dtype=np.int64)
+        recv_fire[0::2] = np.stack([z, t, m1, z], 1)
+        recv_fire[1::2] = np.stack([z + 2, t, deg[j], m1 + 1], 1)
+        events += [np.stack([z + 2, s, deg[i], m1], 1), recv_fire, np.stack([z, s, m1 + 1, z], 1)]
+        tto += [nt + p, nt + 2 * p, nt + 3 * p]
+        nt += 3 * p
+        ne += 4 * p
+        q += p
+    return {"tick_task_off": np.array(tto, dtype=np.int64),
+            "tasks": np.ascontiguousarray(np.concatenate(tasks), dtype=np.int32),
+            "events": np.ascontiguousarray(np.concatenate(events), dtype=np.int32),
+            "n_msgs": 2 * q, "pairs": q}
+
+
+def replay_run(g, v, tr, ticks, persistent):
+    """(device ms, last, flows, caches) of fu_replay on the trace."""
+    h = L.vp()
+    out_ids = np.zeros(1, dtype=np.int32)
+    L.call("fu_replay_create", g.n, L.ptr(g.rowptr), L.ptr(v), ticks, L.ptr(tr["tick_task_off"]), len(tr["tasks"]),
+           L.ptr(tr["tasks"]), len(tr["events"]), L.ptr(tr["events"]), 0, L.ptr(out_ids), tr["n_msgs"], 0, ctypes.byref(h))
+    if persistent:
+        L.call("fu_replay_set_option", h, b"persistent", 1)
+    ms = L.f32()
+    L.call("fu_replay_run_timed", h, ticks, ctypes.byref(ms))
+    last, fl, es = np.empty(g.n), np.empty(g.E), np.empty(g.E)
+    L.call("fu_replay_get", h, L.ptr(last), L.ptr(fl), L.ptr(es))
+    L.lib.fu_replay_destroy(h)
+    return float(ms.value), last, fl, es
+
+
+def same_bits(a, b):
+    return bool(np.array_equal(a.view(np.uint64), b.view(np.uint64)))
+
+
+def against_replay(rounds):
+    g = fu.Graph.random_regular(65536, 8, seed=1)
+    v = fu.uniform_values(g.n, seed=0)
+    t0 = time.perf_counter()
+    tr = build_trace(g, SEED, rounds)
+    t_build = time.perf_counter() - t0
+    with fu.PairwiseSync(g, v, seed=SEED) as eng:
+        eng.run(rounds)  # warm
+        eng.reset()
+        ms_pair = eng.run_timed(rounds)
+        state = (eng.estimates(), eng.flows(), eng.cache())
+        pairs = eng.stats[0]
+    res = {}
+    for pers in (False, True):
+        replay_run(g, v, tr, 3 * rounds, pers)  # warm
+        ms, *st = replay_run(g, v, tr, 3 * rounds, pers)
+        if not all(same_bits(a, b) for a, b in zip(st, state)):
+            raise SystemExit("bench_pair: fu_pair and fu_replay differ on the same events")
+        res[pers] = ms
+    if pairs != tr["pairs"]:
+        raise SystemExit("bench_pair: the engine's pair count differs from the host matching's")
+    ratio = ms_pair / res[True]
+    print(json.dumps({"graph": "rr(n=65536,d=8,seed=1)", "rounds": rounds, "ticks": 3 * rounds, "pairs": pairs,
+                      "parity": "fu_pair bitwise equal to fu_replay (both modes)",
+                      "trace_bytes": int(tr["tasks"].nbytes + tr["events"].nbytes), "trace_build_s": round(t_build, 3),
+                      "pair_us_per_round": round(ms_pair * 1e3 / rounds, 3),
+                      "replay_per_tick_us_per_round": round(res[False] * 1e3 / rounds, 3),
+                      "replay_persistent_us_per_round": round(res[True] * 1e3 / rounds, 3),
+                      "pair_updates_per_s": round(2 * pairs / (ms_pair / 1e3), 1),
+                      "replay_persistent_updates_per_s": round(2 * pairs / (res[True] / 1e3), 1),
+                      "ratio_pair_over_replay_persistent": round(ratio, 4),
+                      "verdict": "win" if ratio < 0.85 else "loss" if ratio > 1.15 else "tie"}), flush=True)
+
+
+def window_us(eng, rounds, reps):
+    """Median device microseconds per round over rounds 1 .. rounds-1, from zero each time, and
+    the pairs of one such window."""
+    t = []
+    for _ in range(reps):
+        eng.reset()
+        eng.run(1)
+        eng.synchronize()
+        first = eng.stats[0]
+        t.append(eng.run_timed(rounds - 1) * 1e3 / (rounds - 1))
+    return statistics.median(t), min(t), eng.stats[0] - first
+
+
+def model_bytes_per_pair(g, seed):
+    """8 (deg_i + deg_j) + 116 averaged over the pairs of rounds 1-4 (host matching)."""
+    deg = np.diff(g.rowptr)
+    tot = cnt = 0
+    for r in range(1, 5):
+        mate, ini = fu.pair_matching(g, seed, r)
+        i = np.flatnonzero(ini)
+        tot += int(np.sum(8 * (deg[i] + deg[mate[i]]) + 116))
+        cnt += len(i)
+    return tot / cnt
+
+
+def big(name, g, rounds, reps, copy_gbs):
+    v = fu.uniform_values(g.n, seed=0)
+    per_pair = model_bytes_per_pair(g, SEED)
+    with fu.PairwiseSync(g, v, seed=SEED) as eng:
+        eng.run(rounds)  # warm
+        ref = None
+        for match in (0, 1):
+            eng.set_option("match", match)
+            t, t_min, pairs = window_us(eng, rounds, reps)
+            state = (eng.estimates(), eng.flows(), eng.cache())
+            if ref is None:
+                ref = state
+            elif not all(same_bits(a, b) for a, b in zip(state, ref)):
+                raise SystemExit("bench_pair: the two forms of the matching differ")
+            ppr = pairs / (rounds - 1)
+            nbytes = ppr * per_pair
+            print(json.dumps({"graph": name, "n": g.n, "E": g.E, "match": ["atomic_min", "listener_scan"][match],
+                              "rounds_timed": [1, rounds - 1], "reps": reps, "us_per_round": round(t, 2),
+                              "us_per_round_min": round(t_min, 2), "pairs_per_round": round(ppr, 1),
+                              "pairs_per_node": round(ppr / g.n, 4), "model_bytes_per_pair": round(per_pair, 1),
+                              "model_bytes_per_round": int(nbytes), "roofline": round(nbytes / PEAK / (t * 1e-6), 5),
+                              "pair_updates_per_s": round(2 * ppr / (t * 1e-6), 1), "copy_GBs": copy_gbs}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=200)
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--skip-replay", action="store_true")
+    a = ap.parse_args()
+    if a.rounds < 2:
+        ap.error("--rounds must be at least 2 (round 0 is not timed)")
+    if not a.skip_replay:
+        against_replay(a.rounds)
+    copy_gbs = round(fu.copy_bandwidth(0), 1)
+    big(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs)
+    big(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs)
+
+
+if __name__ == "__main__":
+    main()
