@@ -143,8 +143,8 @@ int fu_create_from_graph_ex(const fu_graph *g, const double *value, int32_t devi
  * "pack"          gather lossless 8/16/32-bit codes of the estimates once they cluster
  *                 (default 1); "pack_every" rounds between encoding plans (default 16).
  * "stage_layout"  kernel 8, tests: -1 = by packing width, 0..3 = the 1/2/4/8-byte layout.
- * "staged_lo"     kernel 8: staged indices loaded ahead of the flows (1, default) or
- *                 interleaved with them (0; the round-1 order, kept for A/B and tests).
+ * "staged_lo"     accepted and ignored: kernel 8 loads its staged indices ahead of the flows;
+ *                 the interleaved order (0) measured slower and is gone.
  * Removed after measurement (FU_ERR_ARG; the numbers are in DESIGN.md §4 and
  * profiles/MEASUREMENTS.md): "tr_pipe", "hub_prio", "side_tiles", "split_tr", "hub_multi",
  * "hub_blocks", "fuse", "light_geo", "tr_hot" (kernel 9), "hub_cus" / "hub_cu_stride" (the

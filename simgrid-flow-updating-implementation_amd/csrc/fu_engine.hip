@@ -1196,24 +1196,38 @@ __global__ __launch_bounds__(kBlock) void k_isolated(int i0, int n, const double
   if (check) block_max_to(eb, err);
 }
 
-template <bool CHECK, int TE, int TN, bool RF = true, bool LO = true>
+// Kernel 8's light tiles. The tile's flows are taken by global 4-aligned quads: quad g holds
+// edges 4 g .. 4 g + 3, whose split flow words (fhi_idx: a quad never straddles a 32-edge
+// block) are one 16-byte load of high words, one of low words and one 16-byte store of low
+// words. Lane t takes quad (e0 >> 2) + t; LDS slot p holds edge (e0 & ~3) + p, so the tile's
+// own slots are [r, r + ne), r = e0 % 4, and a lane's four slots are 16-byte aligned. A tile
+// of more than TE - r edges ends in a 257th quad: its at most three edges (slots TE .. TE +
+// r - 1) go one each to the first lanes of wave 0. The staged estimates keep the other
+// mapping, element t + 256 k of the tile's slice order to lane t: consecutive lanes read
+// consecutive elements of G, and an estimate meets its flow only in LDS (with the quads'
+// mapping for G too, lane-strided 8-byte loads, the unpacked rounds ran 59.5 against 56.5 us).
+// The edges of a boundary quad outside [e0, e0 + ne) belong to the neighbouring tile, which
+// may be rewriting them in place meanwhile: they are loaded with the quad (the loads stay
+// unconditional, from always-valid addresses, see the load order below), and then dropped:
+// they reach neither LDS nor a sum nor a store, and a boundary quad stores word by word.
+template <bool CHECK, int TE, int TN, bool RF = true>
 __global__ __launch_bounds__(kBlock) void k_round_staged(
     const int4 *__restrict__ tiles, int t0, int ntl,
     const int *__restrict__ rowptr, const int *__restrict__ col,
     const StageArgs sa, const void *__restrict__ G, const double *__restrict__ v,
-    double *__restrict__ F, const double *__restrict__ a_prev, const double *__restrict__ a_prev2,
+    double *F, const double *__restrict__ a_prev, const double *__restrict__ a_prev2,
     double *__restrict__ a_new, const double *__restrict__ target,
     unsigned long long *__restrict__ err, void *__restrict__ code_new, PackCtl *__restrict__ ctl,
     int rslot, int fm) {
-  static_assert(TE % kBlock == 0 && TN <= kBlock, "tile geometry");
+  static_assert(TE == 4 * kBlock && TN <= kBlock, "tile geometry: one quad of edges per lane");
   static_assert(TE <= 1024, "the u16 staged index holds a 10-bit tile position");
   const PackCtl pp = ctl[rslot ^ 1];
   const int lsel = sa.sel[width_index(pp.width)];
   const PackCtl pc = ctl[2];
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl[rslot] = pc;
-  __shared__ double s_x[TE];
-  __shared__ double s_er[TE];
-  __shared__ unsigned char s_own[TE];
+  __shared__ __align__(16) double s_x[TE + 4];
+  __shared__ __align__(16) double s_er[TE + 4];
+  __shared__ __align__(4) unsigned char s_own[TE + 4];
   __shared__ int s_rp[TN + 1];
   __shared__ double s_a[TN];
   const int t = threadIdx.x;
@@ -1225,39 +1239,60 @@ __global__ __launch_bounds__(kBlock) void k_round_staged(
   const int4 tl = tiles[tile];
   const int nb = tl.x, nn = tl.y - tl.x;
   const int e0 = tl.z, ne = tl.w - tl.z;
-  constexpr int kPer = TE / kBlock;
   const unsigned short *__restrict__ s16 = sa.sidx16[lsel];
-  unsigned si[kPer];  // position in the tile
-  double x[kPer], g[kPer];
-  int gi[kPer];
-  // Load order (LO): the run offsets and staged indices first, the flows and node words
-  // after them, so the G loads (which need only the former) issue while the flows are in
-  // flight (in-order completion: waiting for a load waits for every load issued before it).
+  // the flows' split words (fhi_idx). F is not __restrict__ here: the fence below does not
+  // hold back the loads of a noalias argument (the flow loads sank past it, behind the wait
+  // for the staged indices)
+  unsigned *fo = reinterpret_cast<unsigned *>(F);
+  const unsigned *fw = fo;
+  // quads: slot p <-> edge eq0 + p <-> tile position p - r; the tile's slots are [r, pe)
+  const int r = e0 & 3, eq0 = e0 - r, pe = r + ne;
+  const int p0 = 4 * t;
+  bool ok[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) ok[u] = p0 + u >= r && p0 + u < pe;
+  const bool any = ne > 0 && p0 + 3 >= r && p0 < pe;  // the quad holds an edge of the tile
+  const bool full = p0 >= r && p0 + 3 < pe;  // all four are the tile's
+  const int eq = any ? eq0 + p0 : 0;         // quad 0 otherwise: always inside the arrays
+  const bool tok = TE + t < pe;              // the 257th quad: slot TE + t (t < r <= 3)
+  const int et = eq0 + TE + t;
+  unsigned si[4];  // position in the tile
+  double g[4];
+  // the old flows' words as loaded (the high words are kept for the stores); what a quad
+  // holds of a neighbouring tile stays in these registers and goes nowhere
+  uint4 hq = make_uint4(0u, 0u, 0u, 0u), lq = hq;
+  unsigned hwt = 0u, lwt = 0u;
+  int gi[4];
+  // Load order: the run offsets and staged indices first, the flows and node words after
+  // them, so the G loads (which need only the former) issue while the flows are in flight
+  // (in-order completion: waiting for a load waits for every load issued before it). The
+  // interleaved order measured slower.
   int rp;
   double vv, own2;
-  if constexpr (LO) {
   {  // u16 position | run << 10; G index = m + D[run] (lane `run` holds D)
+    // the 257th quad's flows first (a few lanes of the full tiles only): older than the staged
+    // indices, so the counted wait below covers them on either path
+    if constexpr (RF) {
+      if (tok) {
+        const long long i = fhi_idx(et);
+        hwt = fw[i];
+        lwt = fw[i + 32];
+      }
+    }
     const int dl = sa.dtab[lsel][(size_t)tile * kStageRuns + (t & 63)];
-    unsigned short c16[kPer];
-    // unconditional loads from clamped (always valid) indices, so the compiler can wait for
-    // the staged indices alone (vmcnt(N)) instead of for every load (a skipped load would
-    // change the count)
+    // unconditional loads from always-valid addresses, so the compiler can wait for the
+    // staged indices alone (vmcnt(N)) instead of for every load (a skipped load would change
+    // the count)
+    unsigned c16[4];
 #pragma unroll
-    for (int k = 0; k < kPer; ++k) {
+    for (int k = 0; k < 4; ++k) {
       const int q = t + k * kBlock;
-      const unsigned short c = s16[q < ne ? e0 + q : 0];
-      c16[k] = q < ne ? c : (unsigned short)0;
+      c16[k] = s16[q < ne ? e0 + q : 0];
     }
     if constexpr (RF) {
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) {
-        const int q = t + k * kBlock;
-        const double f = ld_f(F, q < ne ? e0 + q : 0);
-        x[k] = q < ne ? f : 0.0;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) x[k] = 0.0;
+      const long long i = fhi_idx(eq);
+      hq = *reinterpret_cast<const uint4 *>(fw + i);
+      lq = *reinterpret_cast<const uint4 *>(fw + i + 32);
     }
     const int tn = min(t, nn - 1);  // a light tile has at least one node
     const int rp0 = rowptr[nb + min(t, nn)];
@@ -1267,72 +1302,63 @@ __global__ __launch_bounds__(kBlock) void k_round_staged(
     vv = t < nn ? v0 : 0.0;
     own2 = t < nn ? o0 : 0.0;
 #pragma unroll
-    for (int k = 0; k < kPer; ++k) {
+    for (int k = 0; k < 4; ++k) {
       const int q = t + k * kBlock;
       const int dd = __shfl(dl, (int)(c16[k] >> 10));
       si[k] = c16[k] & 1023u;
       gi[k] = q < ne ? q + dd : -1;
     }
   }
-  } else {  // the round-1 order: indices and flows interleaved (measured against LO)
-  {  // u16 position | run << 10; G index = m + D[run] (lane `run` holds D)
-    const int dl = sa.dtab[lsel][(size_t)tile * kStageRuns + (t & 63)];
-    unsigned short c16[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int q = t + k * kBlock;
-      c16[k] = q < ne ? s16[e0 + q] : (unsigned short)0;
-      x[k] = q < ne && RF ? ld_f(F, e0 + q) : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int q = t + k * kBlock;
-      const int dd = __shfl(dl, (int)(c16[k] >> 10));
-      si[k] = c16[k] & 1023u;
-      gi[k] = q < ne ? q + dd : -1;
-    }
-  }
-  rp = t <= nn ? rowptr[nb + t] : 0;
-  vv = t < nn ? v[nb + t] : 0.0;
-  own2 = t < nn ? a_prev2[nb + t] : 0.0;
-  }
-  // every G load of the tile first, then decode (escapes gather the double via col)
+  // every G load of the tile first, then decode (escapes gather the double via col). The
+  // loads are unconditional too (index 0 for an edge that is not the tile's), and the 1-, 2-
+  // and 4-byte codes share one path: the aligned 4-byte word that holds the code is loaded
+  // and the code shifted out of it (a load per width in branches of their own made the
+  // compiler drain every load in flight, the flows included, before the 1-byte loads)
   if (pp.width == 0) {
 #pragma unroll
-    for (int k = 0; k < kPer; ++k)
-      g[k] = gi[k] >= 0 ? reinterpret_cast<const double *>(G)[gi[k]] : 0.0;
+    for (int u = 0; u < 4; ++u) {
+      const double d = reinterpret_cast<const double *>(G)[max(gi[u], 0)];
+      g[u] = gi[u] >= 0 ? d : 0.0;
+    }
   } else {
-    unsigned cd[kPer];
-    unsigned esc;
-    if (pp.width == 8) {
-      esc = 0xFFu;
+    const int lb = pp.width == 8 ? 0 : pp.width == 16 ? 1 : 2;  // log2 of the code's bytes
+    const unsigned esc = 0xFFFFFFFFu >> (32 - pp.width);        // the escape code: all ones
+    const char *Gc = reinterpret_cast<const char *>(G);
+    auto ld_word = [&](int i) {  // the word holding code i (codes are aligned to their size)
+      const size_t b = (size_t)max(i, 0) << lb;
+      return *reinterpret_cast<const unsigned *>(Gc + (b & ~(size_t)3));
+    };
+    auto code_of = [&](unsigned w, int i) { return (w >> ((((unsigned)max(i, 0) << lb) & 3u) * 8u)) & esc; };
+    unsigned cd[4];
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) cd[k] = gi[k] >= 0 ? reinterpret_cast<const unsigned char *>(G)[gi[k]] : 0u;
-    } else if (pp.width == 16) {
-      esc = 0xFFFFu;
+    for (int u = 0; u < 4; ++u) cd[u] = ld_word(gi[u]);
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) cd[k] = gi[k] >= 0 ? reinterpret_cast<const unsigned short *>(G)[gi[k]] : 0u;
-    } else {
-      esc = 0xFFFFFFFFu;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) cd[k] = gi[k] >= 0 ? reinterpret_cast<const unsigned *>(G)[gi[k]] : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k)
-      g[k] = gi[k] < 0 ? 0.0 : cd[k] == esc ? a_prev[col[e0 + (int)(si[k] & 0xFFFFu)]] : dkey_inv(pp.base + cd[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < kPer; ++k) {
-    const int q = t + k * kBlock;
-    if (q < ne) {
-      s_x[q] = x[k];
-      s_er[si[k] & 0xFFFFu] = g[k];
+    for (int u = 0; u < 4; ++u) {
+      cd[u] = code_of(cd[u], gi[u]);
+      g[u] = gi[u] < 0 ? 0.0 : cd[u] == esc ? a_prev[col[e0 + (int)si[u]]] : dkey_inv(pp.base + cd[u]);
     }
   }
+  // s_x: the lane's own slots (16-byte writes for a whole quad); s_er: a scatter by position
+  const unsigned hw[4] = {hq.x, hq.y, hq.z, hq.w}, lw[4] = {lq.x, lq.y, lq.z, lq.w};
+  double x[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) x[u] = __hiloint2double((int)hw[u], (int)lw[u]);
+  if (full) {
+    *reinterpret_cast<double2 *>(&s_x[p0]) = make_double2(x[0], x[1]);
+    *reinterpret_cast<double2 *>(&s_x[p0 + 2]) = make_double2(x[2], x[3]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (ok[u]) s_x[p0 + u] = x[u];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (gi[k] >= 0) s_er[r + (int)si[k]] = g[k];
+  if (tok) s_x[TE + t] = __hiloint2double((int)hwt, (int)lwt);
   if (t <= nn) s_rp[t] = rp;
   __syncthreads();
   if (t < nn) {  // phase B (CA:106-113)
-    const int qb = s_rp[t] - e0, qe = s_rp[t + 1] - e0;
+    const int qb = s_rp[t] - eq0, qe = s_rp[t + 1] - eq0;  // the row's slots
     double S = 0.0, T = 0.0;
     const double fo0 = fm ? old_flow(fm, own2) : 0.0;
     for (int q = qb; q < qe; ++q) {
@@ -1350,13 +1376,48 @@ __global__ __launch_bounds__(kBlock) void k_round_staged(
     if (CHECK) eb = err_bits(a, target[nb + t]);
   }
   __syncthreads();
-  // phase C: new flows, coalesced, in place (CA:117-118)
+  // phase C: new flows in place (CA:117-118). A whole quad: its low words are one 16-byte
+  // store, its high words one more when all four changed (or the slots hold no earlier
+  // value, fm), else only those that changed; a boundary quad: its own edges, word by word
+  if (any) {
+    const double2 xa = *reinterpret_cast<const double2 *>(&s_x[p0]), xb = *reinterpret_cast<const double2 *>(&s_x[p0 + 2]);
+    const double2 ea = *reinterpret_cast<const double2 *>(&s_er[p0]), ec = *reinterpret_cast<const double2 *>(&s_er[p0 + 2]);
+    const unsigned ow = *reinterpret_cast<const unsigned *>(&s_own[p0]);
+    const double xs[4] = {xa.x, xa.y, xb.x, xb.y}, es[4] = {ea.x, ea.y, ec.x, ec.y};
+    unsigned nh[4], nl[4];
+    bool ch[4];
 #pragma unroll
-  for (int k = 0; k < kPer; ++k) {
-    const int q = t + k * kBlock;
-    if (q < ne) {
-      st_fo(F, e0 + q, (s_x[q] + s_a[s_own[q]]) - s_er[q], x[k], fm);
+    for (int u = 0; u < 4; ++u) {
+      const int own = ok[u] ? (int)((ow >> (8 * u)) & 0xFFu) : 0;  // (a foreign slot's bytes are dropped)
+      const double f = (xs[u] + s_a[own]) - es[u];
+      nh[u] = (unsigned)__double2hiint(f);
+      nl[u] = (unsigned)__double2loint(f);
+      ch[u] = !RF || fm || nh[u] != hw[u];
     }
+    unsigned *w = fo + fhi_idx(eq);
+    if (full) {
+      *reinterpret_cast<uint4 *>(w + 32) = make_uint4(nl[0], nl[1], nl[2], nl[3]);
+      if (ch[0] && ch[1] && ch[2] && ch[3]) {
+        *reinterpret_cast<uint4 *>(w) = make_uint4(nh[0], nh[1], nh[2], nh[3]);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (ch[u]) st_fw(w + u, nh[u]);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (ok[u]) {
+          st_fw(w + 32 + u, nl[u]);
+          if (ch[u]) st_fw(w + u, nh[u]);
+        }
+    }
+  }
+  if (tok) {
+    const double f = (s_x[TE + t] + s_a[s_own[TE + t]]) - s_er[TE + t];
+    unsigned *w = fo + fhi_idx(et);
+    st_fw(w + 32, (unsigned)__double2loint(f));
+    if (!RF || fm || (unsigned)__double2hiint(f) != hwt) st_fw(w, (unsigned)__double2hiint(f));
   }
   if (CHECK) block_max_to(eb, err);
 }
@@ -2176,7 +2237,6 @@ struct fu_handle {
   int wave_heavy = 1;    // kernel 4: heavy rows one per wave
   int mid_heavy = 1;     // kernel 9: heavy rows of <= 64 x kMidRL edges in a register-resident launch
   int tr_bpx = 32;       // kernel 9: k_transpose blocks per XCD (1 per CU), each looping over buckets; 0 = one per bucket
-  int staged_lo = 1;     // kernel 8: staged indices loaded before the flows (LO)
   int c16 = 1;           // kernel 4: narrow light tiles read 2-byte column offsets
   int multi_mid = 1;     // kernel 9: k_heavy_multi also takes the register launch's rows (257-1024)
   int split_hubs = 1;     // kernel 4: mega-hub tiles alone on the side stream
@@ -2603,17 +2663,16 @@ int launch_k8(fu_handle *h, RoundCtx &c) {
     if (c.err) heavy(std::true_type{});
     else heavy(std::false_type{});
   }
-  // light tiles: rounds 1 and 2 (fm) read no flows (RF = false); LO = staged indices first
+  // light tiles: rounds 1 and 2 (fm) read no flows (RF = false)
   // multi-GPU: the boundary tiles [0, st_nbound), then the halo goes out on the comm stream
   // beside the interior tiles
-  auto light = [&](auto chk, auto rf, auto lo) -> int {
+  auto light = [&](auto chk, auto rf) -> int {
     // multi-GPU: the boundary tiles [0, st_nbound), then the rest
     const int nb = h->dist ? h->st_nbound : 0;
     for (int part = 0; part < 2; ++part) {
       const int t0 = part ? nb : 0, cnt = part ? h->st_ntiles - nb : nb;
       if (cnt)
-        hipLaunchKernelGGL((k_round_staged<decltype(chk)::value, kStageTE, kStageTN, decltype(rf)::value,
-                                           decltype(lo)::value>),
+        hipLaunchKernelGGL((k_round_staged<decltype(chk)::value, kStageTE, kStageTN, decltype(rf)::value>),
                            dim3(cnt), dim3(kBlock), 0, h->stream, h->st_tiles, t0, cnt, h->rowptr, h->col, sa,
                            h->stG, h->v, c.F, c.ap, c.ap2, c.an, h->target, c.err, h->code[r1], h->pctl, r1, c.fm);
       if (!part && h->dist) {  // boundary rows (and the heavy rows) done
@@ -2623,11 +2682,8 @@ int launch_k8(fu_handle *h, RoundCtx &c) {
     }
     return FU_OK;
   };
-  auto light_lo = [&](auto chk, auto rf) {
-    return h->staged_lo ? light(chk, rf, std::true_type{}) : light(chk, rf, std::false_type{});
-  };
   auto light_rf = [&](auto chk) {
-    return c.fm ? light_lo(chk, std::false_type{}) : light_lo(chk, std::true_type{});
+    return c.fm ? light(chk, std::false_type{}) : light(chk, std::true_type{});
   };
   if (h->st_ntiles || h->dist) {
     if (c.err) return light_rf(std::true_type{});
@@ -3153,8 +3209,7 @@ int fu_set_option(fu_handle *h, const char *key, int64_t value) {
     h->split_hubs = value != 0;
     return FU_OK;
   }
-  if (!std::strcmp(key, "staged_lo")) {  // kernel 8: staged indices before the flows (1) or interleaved (0)
-    h->staged_lo = value != 0;
+  if (!std::strcmp(key, "staged_lo")) {  // accepted, no effect: the interleaved order (0) is gone
     return FU_OK;
   }
   if (!std::strcmp(key, "tr_bpx")) {  // kernel 9: transpose blocks per XCD (0 = one per bucket)

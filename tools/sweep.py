@@ -57,7 +57,6 @@ VARIANTS = {
     "deg_np_nosplit": ("recon", {"layout": "degree", "pack": 0, "split_hubs": 0}),
     "stage": ("stage", {}),
     "stage_nopack": ("stage", {"pack": 0}),
-    "stage_lo0": ("stage", {"staged_lo": 0}),
     "stage_pe64": ("stage", {"pack_every": 64}),
 }
 
