@@ -152,7 +152,8 @@ int fu_create_from_graph_ex(const fu_graph *g, const double *value, int32_t devi
  * this round's tiles, profiles/r05/c), "nt" (kernel 4's non-temporal column loads) and "g56"
  * (kernel 8's 7-byte staged codes, profiles/r06/g). */
 int fu_set_option(fu_handle *h, const char *key, int64_t value);
-/* Zero the state: the next round run is round 0. */
+/* Zero the state: the next round run is round 0. Kernel "auto": the unpacked width's cached
+ * winner is back in use (autotune done); a handle never tuned unpacked has a pass pending. */
 int fu_reset(fu_handle *h);
 /* Per-node convergence targets (e.g. exact component means) for the error check. */
 int fu_set_targets(fu_handle *h, const double *target);

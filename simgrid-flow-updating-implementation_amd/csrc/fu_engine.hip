@@ -3290,12 +3290,14 @@ int fu_reset(fu_handle *h) {
   h->seen_width = 0;
   // unpacked again: its winner. A pass still pending for a width the rounds before the reset
   // reached (seen in calls too short for a pass) no longer applies; one armed by the kernel
-  // option still runs.
-  if (h->autotune && (h->tuned || h->tune_for_width) && h->tune_cache[0] >= 0) {
-    use_cand(h, kCands[h->tune_cache[0]]);
+  // option still runs. Where no pass ever ran unpacked (the first one ran at a packed width),
+  // there is no winner to return to: the winner of a packed width would stay in use at width 0
+  // with tuned_width claiming that width, so a pass for width 0 is armed as on a new handle.
+  if (h->autotune && (h->tuned || h->tune_for_width)) {
     h->tuned_width = 0;
-    h->tuned = true;
     h->tune_for_width = false;
+    h->tuned = h->tune_cache[0] >= 0;
+    if (h->tuned) use_cand(h, kCands[h->tune_cache[0]]);
   }
   return FU_OK;
   FU_TRY_END
