@@ -9,6 +9,8 @@ synchronous round that do not run the engine.
     values may change from round to round.
 (c) `delivered_py`: the loss decision on Python ints; `delivered_np` is the same on numpy
     uint64 arrays (wrapping arithmetic) for whole rounds of large graphs.
+
+`tile_census` restates the host's plan of light tiles (fu_lossy_create), from rowptr alone.
 """
 import functools
 
@@ -18,6 +20,7 @@ import coracle
 import fu
 
 M64 = (1 << 64) - 1
+SEED = 11  # the loss seed of the GPU cases and of the conditions on their inputs
 GOLDEN = 0x9E3779B97F4A7C15
 
 
@@ -165,4 +168,97 @@ def hub60():
     d = np.concatenate([leaves, rng.integers(1, 60, 70)])
     g = fu.Graph.from_edges(60, s, d)
     assert int(g.degrees[0]) == 49 and int(g.degrees[1:].max()) < 49
+    return g
+
+
+# ------------------------------------------------------------------------------------
+# the light tiles of fu_lossy_create, and a graph that closes them in every way
+# ------------------------------------------------------------------------------------
+TILE_ROWS, TILE_SLOTS, TILE_HEAVY_DEG = 256, 2048, 128
+
+
+def tile_census(rowptr):
+    """[(first row, end row, slots, why)] of the light tiles that fu_lossy_create plans: rows
+    above degree 128 get a block each and belong to no tile; a tile takes consecutive rows
+    until the graph ends ("end"), it holds 256 rows ("rows"), the next row is above degree 128
+    ("heavy") or the next row would take it past 2048 slots ("slots"), tested in that order."""
+    rp = [int(x) for x in rowptr]
+    n = len(rp) - 1
+    out, i = [], 0
+    while i < n:
+        if rp[i + 1] - rp[i] > TILE_HEAVY_DEG:
+            i += 1
+            continue
+        j = i
+        while True:
+            if j == n:
+                why = "end"
+            elif j - i == TILE_ROWS:
+                why = "rows"
+            elif rp[j + 1] - rp[j] > TILE_HEAVY_DEG:
+                why = "heavy"
+            elif rp[j + 1] - rp[i] > TILE_SLOTS:
+                why = "slots"
+            else:
+                j += 1
+                continue
+            break
+        assert j > i  # a light row alone always fits
+        out.append((i, j, rp[j] - rp[i], why))
+        i = j
+    return out
+
+
+def _undirected(g, first):
+    """The edges (i < j) of g with `first` added to every id."""
+    src = np.repeat(np.arange(g.n), np.diff(g.rowptr))
+    keep = src < g.col
+    return first + src[keep], first + g.col[keep].astype(np.int64)
+
+
+# (name, rows) in id order; the first three end on multiples of 256, so each of their tiles
+# starts where a segment's rows do.
+TILE_SEGMENTS = [("isolated", 256), ("rr3", 1024), ("rr8", 256), ("ring", 64), ("heavy", 1), ("er12", 1000),
+                 ("isolated_tail", 40)]
+
+
+def tile_segment(name):
+    """(first row, rows) of a segment of tile_limit_graph()."""
+    first = 0
+    for s, rows in TILE_SEGMENTS:
+        if s == name:
+            return first, rows
+        first += rows
+    raise KeyError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_limit_graph():
+    """2641 nodes in segments of consecutive ids: 256 isolated rows (a tile of 256 rows and no
+    slot), a random 3-regular graph on 1024 rows (four tiles of 256 rows and 768 slots), a random
+    8-regular graph on 256 rows (256 rows and exactly 2048 slots), a ring of 64 rows that the
+    next row, of degree 129, closes, that row's neighbours being among the 1000 rows of
+    ER(1000, 6000) which follow it (tiles closed by the slot limit), and 40 isolated rows at the
+    end of the last tile."""
+    rng = np.random.default_rng(9)
+    src, dst = [], []
+    for name, make in (("rr3", lambda: fu.Graph.random_regular(1024, 3, seed=2)),
+                       ("rr8", lambda: fu.Graph.random_regular(256, 8, seed=1)),
+                       ("er12", lambda: fu.Graph.erdos_renyi(1000, 6000, seed=4))):
+        s, d = _undirected(make(), tile_segment(name)[0])
+        src.append(s)
+        dst.append(d)
+    r0, rows = tile_segment("ring")
+    src.append(r0 + np.arange(rows))
+    dst.append(r0 + (np.arange(rows) + 1) % rows)
+    e0, rows = tile_segment("er12")
+    src.append(np.full(129, tile_segment("heavy")[0]))
+    dst.append(e0 + rng.choice(rows, size=129, replace=False))
+    n = sum(rows for _, rows in TILE_SEGMENTS)
+    g = fu.Graph.from_edges(n, np.concatenate(src), np.concatenate(dst))
+    deg = g.degrees
+    for name, want in (("isolated", 0), ("rr3", 3), ("rr8", 8), ("ring", 2), ("heavy", 129), ("isolated_tail", 0)):
+        first, rows = tile_segment(name)
+        assert (deg[first:first + rows] == want).all(), name
+    assert int(deg[e0:e0 + 1000].max()) <= TILE_HEAVY_DEG
     return g

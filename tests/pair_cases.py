@@ -24,6 +24,11 @@ from lossy_cases import M64, splitmix_at_py
 
 _MATCHINGS = {}
 
+# The matching seed of the GPU cases and of the conditions on their inputs, and the length of
+# the runs on class_graph().
+SEED = 11
+CLASS_ROUNDS = 40
+
 
 # ------------------------------------------------------------------------------------
 # (a) the matching on Python ints
@@ -200,3 +205,20 @@ def class_graph():
     g = fu.Graph.from_edges(k + n_leaf, np.concatenate(src), np.concatenate(dst))
     assert [int(x) for x in g.degrees[:k]] == CLASS_DEGREES
     return g
+
+
+# At seed 11 the centre of degree 1025 never listens on slot 1024, the only slot of its second
+# chunk, within 40 rounds; at this seed it does in round 4 (test_engine_case_inputs.py).
+LAST_SLOT_SEED, LAST_SLOT_ROUNDS = 252, 6
+
+DENSE66_N, DENSE66_HALF = 6144, 33
+
+
+@functools.lru_cache(maxsize=None)
+def dense66():
+    """The circulant graph on 6144 nodes with neighbours i +- 1 .. i +- 33: every row has degree
+    66, so every pair joins two rows above 64 slots, and a round matches more pairs than the
+    1024 blocks that share the engine's list of them."""
+    i = np.repeat(np.arange(DENSE66_N), DENSE66_HALF)
+    j = (i + np.tile(np.arange(1, DENSE66_HALF + 1), DENSE66_N)) % DENSE66_N
+    return fu.Graph.from_edges(DENSE66_N, i, j)

@@ -126,6 +126,39 @@ def _width_graph():
     return fu.Graph.erdos_renyi(20_000, 80_000, seed=1)
 
 
+# The batched engine's degree boundaries. Light rows (one thread per row and column): loads in
+# groups of four edges, (fr, er) in registers up to degree 16, one block per row above 64.
+# Heavy rows at width K: chunks of ce = 2048 // K edges, so a row of ce + 1 edges is the
+# shortest with two chunks and one of 2 ce + 1 the shortest with three.
+BATCH_LIGHT_DEGREES = [0, 1, 3, 4, 5, 7, 8, 9, 11, 12, 13, 15, 16, 17, 18, 63, 64, 65]
+
+
+def batch_chunk_degrees(K):
+    ce = 2048 // K
+    return [ce - 1, ce, ce + 1, 2 * ce - 1, 2 * ce, 2 * ce + 1]
+
+
+BATCH_BOUNDARY_DEGREES = sorted(set(BATCH_LIGHT_DEGREES).union(*(batch_chunk_degrees(K) for K in range(1, 17))))
+
+
+@functools.lru_cache(maxsize=None)
+def _batch_boundary_graph():
+    """Star centres of exactly BATCH_BOUNDARY_DEGREES (node c has degree
+    BATCH_BOUNDARY_DEGREES[c]), their leaves drawn from a sparse random background graph of 6000
+    nodes that never touches a centre."""
+    rng = np.random.default_rng(13)
+    k, n_leaf = len(BATCH_BOUNDARY_DEGREES), 6000
+    src, dst = [], []
+    for c, d in enumerate(BATCH_BOUNDARY_DEGREES):
+        src.append(np.full(d, c))
+        dst.append(k + rng.choice(n_leaf, size=d, replace=False))
+    src.append(k + rng.integers(0, n_leaf, 2 * n_leaf))
+    dst.append(k + rng.integers(0, n_leaf, 2 * n_leaf))
+    g = fu.Graph.from_edges(k + n_leaf, np.concatenate(src), np.concatenate(dst))
+    assert [int(x) for x in g.degrees[:k]] == BATCH_BOUNDARY_DEGREES
+    return g
+
+
 def _isolated_then_heavy_rows(tail):
     """(n, n_leaf, first isolated row, isolated rows, heavy row, mega hub) of the graph below."""
     n_leaf, n_iso = 12000, 700

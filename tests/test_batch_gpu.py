@@ -14,7 +14,8 @@ import coracle
 import fu
 import oracle
 from conftest import ca_sync_fixtures, load_npz
-from parity_util import FAMILIES, _class_edge_graph, _width_graph, assert_same_bits, count_neg_zero
+from parity_util import (FAMILIES, _batch_boundary_graph, _class_edge_graph, _width_graph, assert_same_bits,
+                         count_neg_zero)
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +152,45 @@ def test_every_width_each_column_equals_its_oracle_run(K):
         assert_same_bits(one.estimates(), refs[WIDTH_ROUNDS][0], "CollectAll estimates")
         assert_same_bits(one.flows(), refs[WIDTH_ROUNDS][1], "CollectAll flows")
         one.close()
+
+
+# ------------------------------------------------------------------------------------
+# 3b. every width against every chunk edge and register boundary
+# ------------------------------------------------------------------------------------
+BOUNDARY_STOPS = (1, 2, 3, 4, 7)
+# Sixteen columns, fixed once; a handle of width K takes the first K. `huge` is left out: its
+# NaNs would hide a difference.
+BOUNDARY_COLUMNS = [("uniform", "wide", "sym", "subn", "neg", "ints", "binade")[c % 7] for c in range(16)]
+
+
+@functools.lru_cache(maxsize=None)
+def _boundary_refs(c):
+    g = _batch_boundary_graph()
+    name = BOUNDARY_COLUMNS[c]
+    v = fu.uniform_values(g.n, seed=40 + c) if name == "uniform" else FAMILIES[name](g.n, seed=40 + c)
+    return v, _oracle_stops(g.arrays(), v, BOUNDARY_STOPS)
+
+
+@pytest.mark.parametrize("K", range(1, 17))
+def test_every_width_on_its_chunk_edges(K):
+    """parity_util._batch_boundary_graph(): heavy rows of ce - 1, ce, ce + 1, 2 ce - 1, 2 ce and
+    2 ce + 1 edges for the chunk ce = 2048 // K of every width (the widths that do not divide
+    2048 included), and light rows on both sides of every group of four, of the register limit
+    and of the heavy limit. Round 1 alone materialises f_0 on demand, rounds 2 and 3 compute
+    the old flows without reading them, round 4 is the first to read the other flow buffer;
+    then reset() and three rounds again."""
+    g = _batch_boundary_graph()
+    cols = [_boundary_refs(c) for c in range(K)]
+    refs = [r for _, r in cols]
+    eng = fu.CollectAllBatch(g, np.stack([v for v, _ in cols], axis=1))
+    for r in BOUNDARY_STOPS:
+        eng.run(r - eng.rounds_done)
+        _check_columns(eng, refs, r, ("K", K))
+    eng.reset()
+    assert eng.rounds_done == 0
+    eng.run(3)
+    _check_columns(eng, refs, 3, ("K", K, "after reset"))
+    eng.close()
 
 
 # ------------------------------------------------------------------------------------

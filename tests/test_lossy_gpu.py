@@ -6,8 +6,10 @@ comparison is by bit pattern, on estimates and flows.
 The graph of most cases is parity_util._class_edge_graph(7): star centres of degrees 0 ... 12000.
 The kernel's row classes change at degree 128 (light tiles / one block per row) and its heavy
 rows are staged in chunks of 2048 slots; 127, 128, 129, 2047, 2048, 2049, 4095, 4096, 4097 and
-8191, 8192, 8193 are all centres of that graph, and its 16000 background rows fill light tiles
-to both of their limits (256 rows, 2048 slots)."""
+8191, 8192, 8193 are all centres of that graph. The slot limit (2048) closes all of its light
+tiles but two (a heavy row closes the first, the end of the graph the last), and none of them
+holds 256 rows or no slot: the cases of section 8 run on lossy_cases.tile_limit_graph(), whose
+tiles close in every way (test_engine_case_inputs.py has the census of both graphs)."""
 import functools
 
 import numpy as np
@@ -17,12 +19,11 @@ import coracle
 import fu
 import oracle
 from conftest import ca_sync_fixtures, load_npz
-from lossy_cases import delivered_np, hashed, hub60, lossy_python, oracle_lossy
+from lossy_cases import (SEED, TILE_ROWS, TILE_SLOTS, delivered_np, hashed, hub60, lossy_python, oracle_lossy, tile_limit_graph,
+                         tile_segment)
 from parity_util import CLASS_EDGE_DEGREES, FAMILIES, _class_edge_graph, assert_same_bits, count_neg_zero
 
 pytestmark = pytest.mark.gpu
-
-SEED = 11
 
 
 def _check(eng, a_ref, f_ref, what):
@@ -281,3 +282,74 @@ def test_one_node_isolated_nodes_and_a_single_edge():
         eng.run(6)
         _check(eng, a, f, ("single edge, p = 1",))
         assert eng.stats == (2 * 5, 2 * 5)
+
+
+# ------------------------------------------------------------------------------------
+# 8. light tiles at the row limit and without slots, under loss
+# ------------------------------------------------------------------------------------
+TILE_STOPS = (1, 2, 5, 9)
+
+
+def _lost(g, delivered, rounds):
+    """The restated count of lost messages of rounds 1 .. rounds-1."""
+    return sum(int((~delivered(r)).sum()) for r in range(1, rounds))
+
+
+@pytest.mark.parametrize("family,p", [("uniform", 0.25), ("uniform", 1.0), ("wide", 0.25)])
+def test_loss_on_tiles_closed_in_every_way(family, p):
+    """Tiles of 256 rows with 0, 768 and 2048 slots, tiles closed by the slot limit, by a heavy
+    row and by the end of the graph, after rounds 1, 2, 5 and 9 against the oracle's replay."""
+    g = tile_limit_graph()
+    v = _values(family, g.n)
+    dl = hashed(p, SEED, g.E)
+    with fu.CollectAllLossy(g, v, loss=p, seed=SEED) as eng:
+        for r in TILE_STOPS:
+            eng.run(r - eng.rounds_done)
+            a, f, _ = oracle_lossy(*g.arrays(), v, r, dl)
+            _check(eng, a, f, (family, "p", p, "round", r))
+            assert eng.stats == (g.E * (r - 1), _lost(g, dl, r)), r
+        if p == 1.0:
+            assert eng.stats == (g.E * 8, g.E * 8)
+
+
+def test_no_loss_on_tiles_closed_in_every_way():
+    g = tile_limit_graph()
+    v = _values("uniform", g.n)
+    with fu.CollectAllLossy(g, v) as eng:
+        for r in TILE_STOPS:
+            eng.run(r - eng.rounds_done)
+            a, f = coracle.ca_sync(*g.arrays(), v, r)
+            _check(eng, a, f, ("p", 0, "round", r))
+            assert eng.stats == (g.E * (r - 1), 0), r
+
+
+def test_outage_of_a_whole_full_tile():
+    """Every slot of the tile of 256 rows and 2048 slots (the 8-regular segment) is down in
+    rounds 3-5, in both directions, at p = 0.25: all its threads take the lost branch, the
+    256th row included, while its neighbours in the plan do not."""
+    g = tile_limit_graph()
+    v = _values("uniform", g.n)
+    first, rows = tile_segment("rr8")
+    assert rows == TILE_ROWS
+    e0, e1 = int(g.rowptr[first]), int(g.rowptr[first + rows])
+    assert e1 - e0 == TILE_SLOTS
+    down = np.zeros(g.E, dtype=np.uint8)
+    down[e0:e1] = 1
+    down[g.rev[e0:e1]] = 1
+    assert int(down.sum()) == TILE_SLOTS  # the segment is closed: every reverse slot is in the tile
+    plain = hashed(0.25, SEED, g.E)
+    masked = hashed(0.25, SEED, g.E, down)
+
+    def delivered(r):
+        return masked(r) if 3 <= r <= 5 else plain(r)
+
+    assert int(plain(3)[e0:e1].sum()) > 0  # the mask takes down slots that the hash delivers
+    with fu.CollectAllLossy(g, v, loss=0.25, seed=SEED) as eng:
+        for r, mask in ((3, None), (4, down), (6, down), (9, None)):  # rounds 0-2, 3, 4-5, 6-8
+            eng.set_link_mask(mask)
+            eng.run(r - eng.rounds_done)
+            a, f, _ = oracle_lossy(*g.arrays(), v, r, delivered)
+            _check(eng, a, f, ("outage of a tile", "round", r))
+            assert eng.stats == (g.E * (r - 1), _lost(g, delivered, r)), r
+    a2, _, _ = oracle_lossy(*g.arrays(), v, 9, plain)
+    assert not np.array_equal(a, a2)

@@ -12,14 +12,12 @@ import pytest
 
 import fu
 from lossy_cases import hub60
-from pair_cases import (BOUNDARY_DEGREES, CLASS_DEGREES, class_graph, oracle_pair, pair_count, pair_python, roles,
-                        rr256_d8)
+from pair_cases import (BOUNDARY_DEGREES, CLASS_DEGREES, CLASS_ROUNDS, LAST_SLOT_ROUNDS, LAST_SLOT_SEED, SEED, class_graph,
+                        dense66, oracle_pair, pair_count, pair_python, roles, rr256_d8)
 from parity_util import FAMILIES, assert_same_bits, count_neg_zero
 
 pytestmark = pytest.mark.gpu
 
-SEED = 11
-CLASS_ROUNDS = 40
 MATCHERS = [0, 1]  # fu_pair_set_option "match": proposers push / listeners scan
 
 
@@ -259,3 +257,58 @@ def test_one_node_two_nodes_no_edges_and_isolated_nodes():
         eng.run(20)
         _check(eng, ref, ("degree-0 nodes beside matched ones",))
         assert eng.stats == (pair_count(*g.arrays(), SEED, 20), 4)
+
+
+# ------------------------------------------------------------------------------------
+# 7. more heavy pairs than blocks, heavy rows paired with heavy rows
+# ------------------------------------------------------------------------------------
+DENSE_ROUNDS = 6
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_ref(rounds):
+    """On pair_cases.dense66() with `wide` values (36 decades of both signs: a misplaced -F1
+    shows in the high bits), from the oracle."""
+    g = dense66()
+    return oracle_pair(*g.arrays(), _values("wide", g.n), rounds, SEED)
+
+
+@pytest.mark.parametrize("match", MATCHERS)
+def test_more_heavy_pairs_than_blocks_round_by_round(match):
+    """Every row of dense66() has 66 slots, so every pair goes to the block-per-pair kernel with
+    both rows above 64, and each of rounds 0-5 lists more than 1024 pairs (asserted in
+    test_engine_case_inputs.py): the blocks take a second pair from the list."""
+    g = dense66()
+    with fu.PairwiseSync(g, _values("wide", g.n), seed=SEED) as eng:
+        eng.set_option("match", match)
+        for r in range(1, DENSE_ROUNDS + 1):
+            eng.run(1)
+            _check(eng, _dense_ref(r), ("match", match, "round", r))
+            assert eng.stats[0] == pair_count(*g.arrays(), SEED, r), r
+        never = g.n - len(set().union(*roles(*g.arrays(), SEED, DENSE_ROUNDS)))
+        assert eng.stats == (pair_count(*g.arrays(), SEED, DENSE_ROUNDS), never)
+
+
+def test_more_heavy_pairs_than_blocks_split_run():
+    g = dense66()
+    with fu.PairwiseSync(g, _values("wide", g.n), seed=SEED) as eng:
+        eng.run(2)
+        eng.run(4)
+        assert eng.rounds_done == DENSE_ROUNDS
+        _check(eng, _dense_ref(DENSE_ROUNDS), ("run(2); run(4)",))
+        assert eng.stats[0] == pair_count(*g.arrays(), SEED, DENSE_ROUNDS)
+
+
+@pytest.mark.parametrize("match", MATCHERS)
+def test_listener_on_the_only_slot_of_its_second_chunk(match):
+    """class_graph() at LAST_SLOT_SEED: in round LAST_SLOT_ROUNDS - 2 the centre of degree 1025
+    listens on slot 1024 (asserted in test_engine_case_inputs.py), so -F1 takes the place of the
+    one element of the row's second chunk. Checked before that round, after it and a round on."""
+    g = class_graph()
+    v = _values("wide", g.n)
+    with fu.PairwiseSync(g, v, seed=LAST_SLOT_SEED) as eng:
+        eng.set_option("match", match)
+        for r in (LAST_SLOT_ROUNDS - 2, LAST_SLOT_ROUNDS - 1, LAST_SLOT_ROUNDS):
+            eng.run(r - eng.rounds_done)
+            _check(eng, oracle_pair(*g.arrays(), v, r, LAST_SLOT_SEED), ("match", match, "round", r))
+        assert eng.stats[0] == pair_count(*g.arrays(), LAST_SLOT_SEED, LAST_SLOT_ROUNDS)
