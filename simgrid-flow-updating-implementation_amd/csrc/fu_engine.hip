@@ -3160,6 +3160,9 @@ int fu_set_option(fu_handle *h, const char *key, int64_t value) {
       const std::string why = rc ? fu_last_error() : "";
       int all_ok = 1;
       if (int rc2 = fu__dist_agree(h, rc == FU_OK, &all_ok)) return rc2;
+      // a rank without a layout (FU_ERR_GRAPH on one GPU) reports what its peers report: the
+      // partition, not the graph, decides which rank it is. The handle keeps its kernel.
+      if (rc == FU_ERR_GRAPH) return fail(FU_ERR_STATE, why);
       if (rc) return fail(rc, why);
       if (!all_ok) return fail(FU_ERR_STATE, "fu_set_option: kernel " + std::to_string(value) + " failed on another rank");
     }

@@ -17,6 +17,10 @@ numbering that fu_dist_create expects:
 * the send lists to rank p are this rank's edges into p's range (ascending global edge
   index) and this rank's nodes adjacent to p's range (ascending id). That is exactly the
   order in which p stores them, so no unpack pass is needed.
+
+No rank is empty: split_ranges never returns an empty range, and partition raises ValueError
+for bounds that have one (or for fewer nodes than ranks) before anything reaches the library.
+A rank may still have no edge, no ghost, no peer, or a single row.
 """
 from __future__ import annotations
 
@@ -29,16 +33,51 @@ from . import _lib as L
 
 
 def split_ranges(rowptr, nranks: int, balance: str = "edges") -> np.ndarray:
-    """Boundaries b[0..nranks] of contiguous node ranges, balanced by edges+nodes."""
+    """Boundaries b[0..nranks] of contiguous node ranges, balanced by edges+nodes
+    (balance "edges") or by nodes alone ("nodes").
+
+    No rank is empty: b[0] = 0, b[nranks] = n and the bounds increase strictly. Where the
+    balance target alone would leave a rank without rows (a hub that outweighs a rank's whole
+    share), the bound moves to the nearest row that keeps one row for every rank, as
+    fu_part.cpp clamps its cell columns: b[p] >= b[p-1] + 1, then b[p] <= n - (nranks - p).
+    A graph of fewer nodes than ranks has no such split: ValueError."""
     rowptr = np.asarray(rowptr, dtype=np.int64)
     n = len(rowptr) - 1
+    nranks = int(nranks)
+    if nranks < 1:
+        raise ValueError(f"split_ranges: nranks must be >= 1, got {nranks}")
+    if n < nranks:
+        raise ValueError(f"split_ranges: {n} nodes cannot give each of {nranks} ranks a row")
     if balance == "nodes":
-        return np.array([(n * p) // nranks for p in range(nranks + 1)], dtype=np.int64)
-    work = rowptr + np.arange(n + 1, dtype=np.int64)  # edges + nodes prefix
-    targets = [(work[-1] * p) // nranks for p in range(nranks + 1)]
-    b = np.searchsorted(work, targets, side="left").astype(np.int64)
-    b[0], b[-1] = 0, n
-    return np.maximum.accumulate(b)
+        b = np.array([(n * p) // nranks for p in range(nranks + 1)], dtype=np.int64)
+    else:
+        work = rowptr + np.arange(n + 1, dtype=np.int64)  # edges + nodes prefix
+        targets = [(work[-1] * p) // nranks for p in range(nranks + 1)]
+        b = np.searchsorted(work, targets, side="left").astype(np.int64)
+        b[0], b[-1] = 0, n
+        b = np.maximum.accumulate(b)
+    for p in range(1, nranks):
+        b[p] = max(b[p], b[p - 1] + 1)
+    for p in range(nranks - 1, 0, -1):
+        b[p] = min(b[p], n - (nranks - p))
+    return b
+
+
+def check_bounds(bounds, n: int, nranks: int) -> np.ndarray:
+    """`bounds` as int64 [nranks + 1] if it cuts [0, n) into nranks non-empty ranges in order;
+    ValueError naming the first rank whose range is wrong otherwise."""
+    b = np.asarray(bounds, dtype=np.int64)
+    if b.shape != (nranks + 1,):
+        raise ValueError(f"partition: bounds must have nranks + 1 = {nranks + 1} entries, got shape {b.shape}")
+    if b[0] != 0:
+        raise ValueError(f"partition: rank 0 must start at node 0, not {int(b[0])}")
+    for p in range(nranks):
+        if b[p + 1] <= b[p]:
+            what = "is empty" if b[p + 1] == b[p] else "runs backwards (bounds not monotone)"
+            raise ValueError(f"partition: rank {p}'s range [{int(b[p])}, {int(b[p + 1])}) {what}")
+    if b[-1] != n:
+        raise ValueError(f"partition: rank {nranks - 1} must end at node n = {n}, not {int(b[-1])}")
+    return b
 
 
 @dataclass
@@ -71,10 +110,19 @@ class Plan:
 
 
 def partition(rowptr, col, rev, nranks: int, rank: int, bounds=None) -> Plan:
+    """Rank `rank`'s plan of the cut at `bounds` (default: split_ranges(rowptr, nranks)).
+
+    No rank is empty. Bounds that are not monotone, leave a rank without rows or do not run
+    from 0 to n raise ValueError naming the rank, here on the host: a rank without rows has no
+    handle (fu_dist_create refuses n_local = 0), and on the RCCL transport its peers would
+    already be waiting for it inside the communicator's creation."""
     rowptr = np.asarray(rowptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int64)
     rev = np.asarray(rev, dtype=np.int64)
-    b = split_ranges(rowptr, nranks) if bounds is None else np.asarray(bounds, dtype=np.int64)
+    nranks = int(nranks)
+    if not 0 <= rank < nranks:
+        raise ValueError(f"partition: rank {rank} is not in [0, {nranks})")
+    b = split_ranges(rowptr, nranks) if bounds is None else check_bounds(bounds, len(rowptr) - 1, nranks)
     lo, hi = int(b[rank]), int(b[rank + 1])
     e0, e1 = int(rowptr[lo]), int(rowptr[hi])
     n_local, e_local = hi - lo, e1 - e0
