@@ -15,23 +15,12 @@
 // column index, the row pointers and the degree are read once for all columns. Offsets are
 // 64-bit (E * K may pass 2^31). State as in the scalar engine: F[r & 1] updated in place
 // (f_{r-2} -> f_r), A[r % 3] = a_r.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "fu_common.h"
+//
+// The handle scaffold (create and destroy, the run loops, the error slots, the small entry
+// points) is csrc/fu_handle.h, shared with the lossy and pairwise engines.
+#include "fu_handle.h"
 
 using namespace fu;
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 namespace {
 
@@ -246,92 +235,51 @@ inline unsigned grid_for(i64 work) { return (unsigned)((work + kBlock - 1) / kBl
 
 }  // namespace
 
-struct fu_batch {
-  int device = 0;
-  int32_t n = 0, k = 0;
-  int64_t E = 0;
-  int64_t round = 0;
-  bool has_target = false;
+struct fu_batch : handle_base {  // width = K
+  static constexpr const char *kTag = "fu_batch";
   int32_t n_heavy = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   i64 *rowptr = nullptr;
   int *col = nullptr, *hrows = nullptr;
-  double *v = nullptr, *target = nullptr, *a[3] = {nullptr, nullptr, nullptr}, *f[2] = {nullptr, nullptr};
-  unsigned long long *err = nullptr;
-  int64_t errcap = 0;
+  double *v = nullptr, *a[3] = {nullptr, nullptr, nullptr}, *f[2] = {nullptr, nullptr};
 };
 
-namespace {
-
-template <typename T>
-int dmalloc(T **p, int64_t count) {
-  if (hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
-    *p = nullptr;
-    return fail(FU_ERR_ALLOC, "fu_batch: hipMalloc failed");
-  }
-  return FU_OK;
-}
-
-int set_device(fu_batch *b) {
-  HIP_TRY(hipSetDevice(b->device));
-  return FU_OK;
-}
-
-int err_slots(fu_batch *b, int64_t count) {
-  if (count <= b->errcap) return FU_OK;
-  if (b->err) hipFree(b->err);
-  b->err = nullptr;
-  b->errcap = 0;
-  if (int rc = dmalloc(&b->err, count)) return rc;
-  b->errcap = count;
-  return FU_OK;
-}
-
-int launch_err(fu_batch *b, unsigned long long *slot) {
-  const i64 total = (i64)b->n * b->k;
-  const int tb = (kBlock / b->k) * b->k;
+static int launch_err(fu_batch *b, u64 *slot) {
+  const int K = b->width;
+  const i64 total = (i64)b->n * K;
+  const int tb = (kBlock / K) * K;
   const unsigned grid = (unsigned)std::min<i64>(1024, (total + tb - 1) / tb);
-  hipLaunchKernelGGL(kb_max_err, dim3(grid), dim3(kBlock), 0, b->stream, total, b->k,
-                     b->a[(b->round + 2) % 3], b->target, slot);  // a_{round-1}: the last round run
+  hipLaunchKernelGGL(kb_max_err, dim3(grid), dim3(kBlock), 0, b->stream, total, K, b->a[(b->round + 2) % 3], b->target,
+                     slot);  // a_{round-1}: the last round run
   HIP_TRY(hipGetLastError());
   return FU_OK;
 }
 
-int launch_round(fu_batch *b) {
+static int launch_round(fu_batch *b) {
   const int64_t r = b->round;
-  const i64 total = (i64)b->n * b->k;
+  const int K = b->width;
+  const i64 total = (i64)b->n * K;
   if (r == 0) {
-    hipLaunchKernelGGL(kb_round0, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, b->k, b->rowptr, b->v,
-                       b->a[0], b->a[2]);
+    hipLaunchKernelGGL(kb_round0, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, K, b->rowptr, b->v, b->a[0],
+                       b->a[2]);
   } else {
     const int fm = r == 1 ? 1 : r == 2 ? 2 : 0;
     double *a1 = b->a[(r + 2) % 3], *a2 = b->a[(r + 1) % 3], *ao = b->a[r % 3], *F = b->f[r & 1];
-    hipLaunchKernelGGL(kb_light, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, b->k, fm, b->rowptr, b->col,
-                       b->v, a1, a2, ao, F);
+    hipLaunchKernelGGL(kb_light, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, K, fm, b->rowptr, b->col, b->v,
+                       a1, a2, ao, F);
     if (b->n_heavy > 0)
-      hipLaunchKernelGGL(kb_heavy, dim3(b->n_heavy), dim3(kBlock), 0, b->stream, b->k, fm, b->hrows, b->rowptr, b->col,
-                         b->v, a1, a2, ao, F);
+      hipLaunchKernelGGL(kb_heavy, dim3(b->n_heavy), dim3(kBlock), 0, b->stream, K, fm, b->hrows, b->rowptr, b->col, b->v,
+                         a1, a2, ao, F);
   }
   HIP_TRY(hipGetLastError());
   b->round = r + 1;
   return FU_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int fu_batch_destroy(fu_batch *b) {
-  if (!b) return fail(FU_ERR_ARG, "fu_batch_destroy: bad arguments");
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  for (void *p : {(void *)b->rowptr, (void *)b->col, (void *)b->hrows, (void *)b->v, (void *)b->target, (void *)b->a[0],
-                  (void *)b->a[1], (void *)b->a[2], (void *)b->f[0], (void *)b->f[1], (void *)b->err})
-    if (p) (void)hipFree(p);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
+  if (!b) return bad_arguments<fu_batch>("destroy");
+  handle_close(b, {b->rowptr, b->col, b->hrows, b->v, b->a[0], b->a[1], b->a[2], b->f[0], b->f[1]});
   delete b;
   return FU_OK;
 }
@@ -341,67 +289,37 @@ int fu_batch_destroy(fu_batch *b) {
 int fu_batch_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev, int32_t k,
                     const double *value, int32_t device, fu_batch **out) {
   FU_TRY_BEGIN
-  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return fail(FU_ERR_ARG, "fu_batch_create: bad arguments");
+  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_batch>("create");
   if (k < 1 || k > kMaxK) return fail(FU_ERR_ARG, "fu_batch_create: k must be in 1..16, got " + std::to_string(k));
-  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, "fu_batch_create: rowptr[0] must be 0 and rowptr[n] == e");
+  if (int rc = check_csr("fu_batch_create", n, e, rowptr, col)) return rc;
+  // The flow reconstruction needs every i -> j to have its j -> i and nothing else of rev,
+  // which never reaches the device: a caller's rev is checked for that alone.
+  if (e > 0)
+    if (int rc = rev ? check_rev("fu_batch_create", RevCheck::kSymmetric, n, rowptr, col, rev)
+                     : rev_of_csr(n, e, rowptr, col, nullptr))
+      return rc;
   std::vector<int32_t> heavy;
-  for (int32_t i = 0; i < n; ++i) {
-    if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, "fu_batch_create: rowptr not monotone");
+  for (int32_t i = 0; i < n; ++i)
     if (rowptr[i + 1] - rowptr[i] > kHeavyDeg) heavy.push_back(i);
-  }
-  for (int64_t q = 0; q < e; ++q)
-    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, "fu_batch_create: col index out of range at edge " + std::to_string(q));
-  if (e > 0 && !rev) {  // the flow reconstruction needs every i -> j to have its j -> i
-    fu_graph g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + e);
-    if (int rc = fu::build_rev(g)) return rc;
-  } else if (e > 0) {
-    for (int32_t i = 0; i < n; ++i)
-      for (int64_t q = rowptr[i]; q < rowptr[i + 1]; ++q) {
-        const int32_t j = col[q];
-        const int64_t r = rev[q];
-        if (r < rowptr[j] || r >= rowptr[j + 1] || col[r] != i)
-          return fail(FU_ERR_GRAPH, "fu_batch_create: rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
-                                        std::to_string(q));
-      }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, "fu_batch_create: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, "fu_batch_create: device out of range");
   auto *b = new fu_batch();
-  b->device = device;
-  b->n = n;
-  b->k = k;
-  b->E = e;
   b->n_heavy = (int32_t)heavy.size();
   auto cleanup = [&](int code) { fu_batch_destroy(b); return code; };
   int rc = FU_OK;
-  if ((rc = set_device(b))) return cleanup(rc);
-  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_batch_create: hipStreamCreate failed"));
-  if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_batch_create: hipEventCreate failed"));
-  const int64_t nk = (int64_t)n * k, ek = e * k;
-  if ((rc = dmalloc(&b->rowptr, (int64_t)n + 1)) || (rc = dmalloc(&b->col, e)) || (rc = dmalloc(&b->hrows, b->n_heavy)) ||
-      (rc = dmalloc(&b->v, nk)) || (rc = dmalloc(&b->target, nk)) || (rc = dmalloc(&b->a[0], nk)) ||
-      (rc = dmalloc(&b->a[1], nk)) || (rc = dmalloc(&b->a[2], nk)) || (rc = dmalloc(&b->f[0], ek)) ||
-      (rc = dmalloc(&b->f[1], ek)) || (rc = err_slots(b, k)))
+  if ((rc = handle_open(b, device, n, e, k))) return cleanup(rc);
+  const int64_t nk = (int64_t)n * k, ek = std::max<int64_t>(e * k, 1);
+  if ((rc = dmalloc(b, &b->rowptr, (int64_t)n + 1)) || (rc = dmalloc(b, &b->col, e)) ||
+      (rc = dmalloc(b, &b->hrows, b->n_heavy)) || (rc = dmalloc(b, &b->v, nk)) || (rc = dmalloc(b, &b->a[0], nk)) ||
+      (rc = dmalloc(b, &b->a[1], nk)) || (rc = dmalloc(b, &b->a[2], nk)) || (rc = dmalloc(b, &b->f[0], ek)) ||
+      (rc = dmalloc(b, &b->f[1], ek)))
     return cleanup(rc);
   static_assert(sizeof(i64) == sizeof(int64_t), "rowptr is uploaded as is");
-  if (hipMemcpy(b->rowptr, rowptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess ||
-      (e && hipMemcpy(b->col, col, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
-      (b->n_heavy && hipMemcpy(b->hrows, heavy.data(), sizeof(int32_t) * heavy.size(), hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(b->v, value, sizeof(double) * (size_t)nk, hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_batch_create: upload failed"));
-  if ((e == 0 && hipMemset(b->col, 0, sizeof(int32_t)) != hipSuccess) ||
-      hipMemset(b->a[0], 0, sizeof(double) * (size_t)nk) != hipSuccess ||
-      hipMemset(b->a[1], 0, sizeof(double) * (size_t)nk) != hipSuccess ||
-      hipMemset(b->a[2], 0, sizeof(double) * (size_t)nk) != hipSuccess ||
-      hipMemset(b->f[0], 0, sizeof(double) * (size_t)std::max<int64_t>(ek, 1)) != hipSuccess ||
-      hipMemset(b->f[1], 0, sizeof(double) * (size_t)std::max<int64_t>(ek, 1)) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_batch_create: memset failed"));
+  if ((rc = put(b, b->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(b, b->col, col, e)) ||
+      (rc = put(b, b->hrows, heavy.data(), b->n_heavy)) || (rc = put(b, b->v, value, nk)))
+    return cleanup(rc);
+  // without edges col is one element, and it is written too (the other engines leave theirs)
+  if ((rc = zero(b, b->col, e == 0 ? 1 : 0)) || (rc = zero(b, b->a[0], nk)) || (rc = zero(b, b->a[1], nk)) ||
+      (rc = zero(b, b->a[2], nk)) || (rc = zero(b, b->f[0], ek)) || (rc = zero(b, b->f[1], ek)))
+    return cleanup(rc);
   *out = b;
   return FU_OK;
   FU_TRY_END
@@ -409,135 +327,54 @@ int fu_batch_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
 
 int fu_batch_create_from_graph(const fu_graph *g, int32_t k, const double *value, int32_t device, fu_batch **out) {
   FU_TRY_BEGIN
-  if (!g || !value || !out) return fail(FU_ERR_ARG, "fu_batch_create_from_graph: bad arguments");
-  if (k < 1 || k > kMaxK) return fail(FU_ERR_ARG, "fu_batch_create_from_graph: k must be in 1..16, got " + std::to_string(k));
-  const int64_t E = g->rowptr[g->n];
-  if ((int64_t)g->rev.size() != E) return fail(FU_ERR_GRAPH, "fu_batch_create_from_graph: graph is not symmetric");
-  return fu_batch_create(g->n, E, g->rowptr.data(), g->col.data(), E ? g->rev.data() : nullptr, k, value, device, out);
+  if (g && value && out && (k < 1 || k > kMaxK))  // after the null checks, before the graph's
+    return fail(FU_ERR_ARG, "fu_batch_create_from_graph: k must be in 1..16, got " + std::to_string(k));
+  return create_from_graph<fu_batch>(g, value, out, [&](auto... csr) { return fu_batch_create(csr..., k, value, device, out); });
   FU_TRY_END
 }
 
 int fu_batch_reset(fu_batch *b) {
-  if (!b) return fail(FU_ERR_ARG, "fu_batch_reset: bad arguments");
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (!b) return bad_arguments<fu_batch>("reset");
+  if (int rc = synchronize(b)) return rc;
   b->round = 0;  // round 0 rewrites a_0 and a_{-1}; rounds 1 and 2 write their flows without reading any
   return FU_OK;
 }
 
-int fu_batch_set_targets(fu_batch *b, const double *target) {
-  FU_TRY_BEGIN
-  if (!b || !target) return fail(FU_ERR_ARG, "fu_batch_set_targets: bad arguments");
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipMemcpyAsync(b->target, target, sizeof(double) * (size_t)b->n * b->k, hipMemcpyHostToDevice, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  b->has_target = true;
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_batch_run(fu_batch *b, int32_t rounds, int32_t err_every, double *err_trace) {
-  FU_TRY_BEGIN
-  if (!b || rounds < 0) return fail(FU_ERR_ARG, "fu_batch_run: bad arguments");
-  if (err_every > 0 && !b->has_target) return fail(FU_ERR_STATE, "fu_batch_run: err_every > 0 needs fu_batch_set_targets");
-  if (int rc = set_device(b)) return rc;
-  const int64_t nerr = err_every > 0 ? rounds / err_every : 0;
-  if (nerr > 0) {
-    if (int rc = err_slots(b, nerr * b->k)) return rc;
-    HIP_TRY(hipMemsetAsync(b->err, 0, sizeof(unsigned long long) * (size_t)(nerr * b->k), b->stream));
-  }
-  for (int32_t r = 0; r < rounds; ++r) {
-    if (int rc = launch_round(b)) return rc;
-    if (nerr > 0 && (r + 1) % err_every == 0)
-      if (int rc = launch_err(b, b->err + (int64_t)((r + 1) / err_every - 1) * b->k)) return rc;
-  }
-  if (nerr > 0) {
-    std::vector<unsigned long long> bits((size_t)(nerr * b->k));
-    HIP_TRY(hipMemcpyAsync(bits.data(), b->err, sizeof(unsigned long long) * bits.size(), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (err_trace) std::memcpy(err_trace, bits.data(), sizeof(double) * bits.size());
-  }
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_batch_run_timed(fu_batch *b, int32_t rounds, float *ms) {
-  FU_TRY_BEGIN
-  if (!b || !ms || rounds < 0) return fail(FU_ERR_ARG, "fu_batch_run_timed: bad arguments");
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));
-  for (int32_t r = 0; r < rounds; ++r)
-    if (int rc = launch_round(b)) return rc;
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  HIP_TRY(hipEventSynchronize(b->ev1));
-  HIP_TRY(hipEventElapsedTime(ms, b->ev0, b->ev1));
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_batch_max_err(fu_batch *b, double *out) {
-  FU_TRY_BEGIN
-  if (!b || !out) return fail(FU_ERR_ARG, "fu_batch_max_err: bad arguments");
-  if (!b->has_target) return fail(FU_ERR_STATE, "fu_batch_max_err: call fu_batch_set_targets first");
-  if (b->round == 0) return fail(FU_ERR_STATE, "fu_batch_max_err: no round has run");
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipMemsetAsync(b->err, 0, sizeof(unsigned long long) * b->k, b->stream));
-  if (int rc = launch_err(b, b->err)) return rc;
-  unsigned long long bits[kMaxK];
-  HIP_TRY(hipMemcpyAsync(bits, b->err, sizeof(unsigned long long) * b->k, hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  std::memcpy(out, bits, sizeof(double) * b->k);
-  return FU_OK;
-  FU_TRY_END
-}
+int fu_batch_set_targets(fu_batch *b, const double *target) { return set_targets(b, target); }
+int fu_batch_run(fu_batch *b, int32_t rounds, int32_t err_every, double *err_trace) { return run(b, rounds, err_every, err_trace); }
+int fu_batch_run_timed(fu_batch *b, int32_t rounds, float *ms) { return run_timed(b, rounds, ms); }
+int fu_batch_max_err(fu_batch *b, double *out) { return max_err(b, out, /*needs_a_round=*/true); }
+int fu_batch_get_round(fu_batch *b, int64_t *rounds_done) { return get_round(b, rounds_done); }
+int fu_batch_synchronize(fu_batch *b) { return synchronize(b); }
 
 int fu_batch_get_estimates(fu_batch *b, double *a_out) {
-  FU_TRY_BEGIN
-  if (!b || !a_out) return fail(FU_ERR_ARG, "fu_batch_get_estimates: bad arguments");
-  const size_t nk = (size_t)b->n * b->k;
+  if (!b || !a_out) return bad_arguments<fu_batch>("get_estimates");
+  const size_t nk = (size_t)b->n * b->width;
   if (b->round == 0) {  // zero state
     std::fill(a_out, a_out + nk, 0.0);
     return FU_OK;
   }
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipMemcpyAsync(a_out, b->a[(b->round + 2) % 3], sizeof(double) * nk, hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return FU_OK;
-  FU_TRY_END
+  return download(b, a_out, b->a[(b->round + 2) % 3], sizeof(double) * nk);
 }
 
 int fu_batch_get_flows(fu_batch *b, double *f_out) {
   FU_TRY_BEGIN
-  if (!b || (!f_out && b->E)) return fail(FU_ERR_ARG, "fu_batch_get_flows: bad arguments");
+  if (!b || (!f_out && b->E)) return bad_arguments<fu_batch>("get_flows");
   if (b->E == 0) return FU_OK;
-  const size_t ek = (size_t)b->E * b->k;
+  const size_t ek = (size_t)b->E * b->width;
   if (b->round == 0) {  // zero state
     std::fill(f_out, f_out + ek, 0.0);
     return FU_OK;
   }
-  if (int rc = set_device(b)) return rc;
   if (b->round == 1) {  // round 0 wrote no flows: f_0 on demand (round 2 never reads it from memory)
-    const i64 total = (i64)b->n * b->k;
-    hipLaunchKernelGGL(kb_flows0, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, b->k, b->rowptr, b->a[0], b->f[0]);
+    if (int rc = set_device(b)) return rc;
+    const i64 total = (i64)b->n * b->width;
+    hipLaunchKernelGGL(kb_flows0, dim3(grid_for(total)), dim3(kBlock), 0, b->stream, total, b->width, b->rowptr, b->a[0],
+                       b->f[0]);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(f_out, b->f[(b->round - 1) & 1], sizeof(double) * ek, hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return FU_OK;
+  return download(b, f_out, b->f[(b->round - 1) & 1], sizeof(double) * ek);
   FU_TRY_END
-}
-
-int fu_batch_get_round(fu_batch *b, int64_t *rounds_done) {
-  if (!b || !rounds_done) return fail(FU_ERR_ARG, "fu_batch_get_round: bad arguments");
-  *rounds_done = b->round;
-  return FU_OK;
-}
-
-int fu_batch_synchronize(fu_batch *b) {
-  if (!b) return fail(FU_ERR_ARG, "fu_batch_synchronize: bad arguments");
-  if (int rc = set_device(b)) return rc;
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return FU_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,20 @@ struct fu_graph {
 namespace fu {
 // Builds rev for g (fails if some i->j lacks j->i). Parallel, deterministic.
 int build_rev(fu_graph &g);
+
+// What fu_batch_create, fu_lossy_create and fu_pair_create ask of a caller's CSR, on the host
+// and before any HIP call; `who` is the entry point's name, for the message.
+// rowptr[0] == 0, rowptr[n] == e, rowptr monotone, every col in [0, n).
+int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col);
+// rev against a CSR that passed check_csr. kSymmetric: rev[k] lies in the row of k's neighbour
+// at a slot that points back, which proves the graph symmetric (the batched engine never reads
+// rev on the device). kPairing: rev is an involution as well (the lossy and pairwise engines
+// gather through it: anything less would be an out-of-bounds or wrong access there).
+enum class RevCheck { kSymmetric, kPairing };
+int check_rev(const char *who, RevCheck level, int32_t n, const int64_t *rowptr, const int32_t *col, const int32_t *rev);
+// build_rev for a caller's CSR: the reverse-edge index in *rev, or with rev == nullptr only
+// the verdict (FU_ERR_GRAPH if some i -> j lacks its j -> i).
+int rev_of_csr(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, std::vector<int32_t> *rev);
 }  // namespace fu
 
 #define FU_TRY_BEGIN try {

@@ -131,6 +131,38 @@ int build_rev(fu_graph &g) {
   return FU_OK;
 }
 
+int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col) {
+  const std::string w(who);
+  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, w + ": rowptr[0] must be 0 and rowptr[n] == e");
+  for (int32_t i = 0; i < n; ++i)
+    if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, w + ": rowptr not monotone");
+  for (int64_t q = 0; q < e; ++q)
+    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, w + ": col index out of range at edge " + std::to_string(q));
+  return FU_OK;
+}
+
+int check_rev(const char *who, RevCheck level, int32_t n, const int64_t *rowptr, const int32_t *col, const int32_t *rev) {
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int32_t j = col[k];
+      const int64_t r = rev[k];
+      if (r < rowptr[j] || r >= rowptr[j + 1] || col[r] != i || (level == RevCheck::kPairing && rev[r] != k))
+        return fail(FU_ERR_GRAPH, std::string(who) + ": rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
+                                      std::to_string(k));
+    }
+  return FU_OK;
+}
+
+int rev_of_csr(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, std::vector<int32_t> *rev) {
+  fu_graph g;
+  g.n = n;
+  g.rowptr.assign(rowptr, rowptr + n + 1);
+  g.col.assign(col, col + e);
+  if (int rc = build_rev(g)) return rc;
+  if (rev) rev->swap(g.rev);
+  return FU_OK;
+}
+
 }  // namespace fu
 
 using namespace fu;

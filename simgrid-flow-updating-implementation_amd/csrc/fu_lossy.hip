@@ -16,24 +16,12 @@
 //
 // Slot k of round r >= 1 is lost iff down[k] != 0 or u01(splitmix_at(splitmix_at(seed, r), k))
 // < p, with k the caller's slot index: no mask memory, no dependence on the launch shape.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "fu_common.h"
+//
+// The handle scaffold (create and destroy, the run loops, the error slots and k_max_err, the
+// small entry points) is csrc/fu_handle.h, shared with the batched and pairwise engines.
+#include "fu_handle.h"
 
 using namespace fu;
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 namespace {
 
@@ -44,7 +32,6 @@ constexpr int kHeavyDeg = 128;     // rows above this degree run one block per r
 constexpr int kChunk = 2048;       // heavy rows: (F, E) elements staged in LDS per chunk
 
 using i64 = long long;
-using u64 = unsigned long long;
 
 // The key of round r's decisions, and the decision itself: the kernels and
 // fu_lossy_delivered share both. The compare is fp64 on both sides.
@@ -81,20 +68,6 @@ __device__ inline bool fetch(const RoundArgs &A, i64 k, double &F, double &E) {
     E = A.a_old[A.col[k]];
   }
   return lost;
-}
-
-// One atomic per block that lost something.
-__device__ inline void block_count_to(int cnt, u64 *dst) {
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-  __shared__ int s_w[kBlock / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) s_w[w] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int q = 0; q < kBlock / 64; ++q) t += s_w[q];
-    if (t) atomicAdd(dst, (u64)t);
-  }
 }
 
 // Light tiles: consecutive rows of degree <= kHeavyDeg, at most kTileRows rows and
@@ -175,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void kl_light(RoundArgs A, const int2 *__re
   }
   __syncthreads();
   for (int q = tid; q < ne; q += kBlock) A.f_new[e0 + q] = s_F[q];
-  if (!A.zero) block_count_to(cnt, A.lost);
+  if (!A.zero) block_count_to<kBlock>(cnt, A.lost);  // one atomic per block that lost something
 }
 
 // Rows above kHeavyDeg: one block per row. All threads load a chunk of slots coalesced and
@@ -224,84 +197,30 @@ __global__ __launch_bounds__(kBlock) void kl_heavy(RoundArgs A, const int *__res
     const bool lost = fetch(A, b + q, F, E);
     A.f_new[b + q] = (F + a) - (lost ? own : E);
   }
-  if (!A.zero) block_count_to(cnt, A.lost);
-}
-
-// max_i |a_i - target_i| as a uint64 bit pattern, the rule of the scalar engine's k_max_err:
-// non-negative doubles order like their bits, and a NaN with its sign cleared is above +inf,
-// so one NaN makes the result NaN.
-__global__ __launch_bounds__(kBlock) void kl_max_err(int n, const double *__restrict__ a,
-                                                     const double *__restrict__ target, u64 *__restrict__ err) {
-  u64 m = 0;
-  for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < n; i += (i64)gridDim.x * kBlock) {
-    const u64 x = (u64)__double_as_longlong(fabs(a[i] - target[i]));
-    m = x > m ? x : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 y = __shfl_xor(m, off, 64);
-    m = m > y ? m : y;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
+  if (!A.zero) block_count_to<kBlock>(cnt, A.lost);
 }
 
 }  // namespace
 
-struct fu_lossy {
-  int device = 0;
-  int32_t n = 0;
-  int64_t E = 0;
-  int64_t round = 0;
+struct fu_lossy : handle_base {
+  static constexpr const char *kTag = "fu_lossy";
   double p = 0.0;
   uint64_t seed = 0;
-  bool has_target = false, has_mask = false;
+  bool has_mask = false;
   int32_t n_tiles = 0, n_heavy = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   i64 *rowptr = nullptr;
   int *col = nullptr, *rev = nullptr, *hrows = nullptr;
   int2 *tiles = nullptr;
   unsigned char *down = nullptr;
-  double *v = nullptr, *target = nullptr, *a[2] = {nullptr, nullptr}, *f[2] = {nullptr, nullptr};
+  double *v = nullptr, *a[2] = {nullptr, nullptr}, *f[2] = {nullptr, nullptr};
   u64 *lost = nullptr;
-  u64 *err = nullptr;
-  int64_t errcap = 0;
 };
 
-namespace {
-
-template <typename T>
-int dmalloc(T **p, int64_t count) {
-  if (hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
-    *p = nullptr;
-    return fail(FU_ERR_ALLOC, "fu_lossy: hipMalloc failed");
-  }
-  return FU_OK;
+static int launch_err(fu_lossy *h, u64 *slot) {
+  return launch_max_err<kBlock>(h, h->a[(h->round + 1) & 1], slot);  // a of the last round run
 }
 
-int set_device(fu_lossy *h) {
-  HIP_TRY(hipSetDevice(h->device));
-  return FU_OK;
-}
-
-int err_slots(fu_lossy *h, int64_t count) {
-  if (count <= h->errcap) return FU_OK;
-  if (h->err) hipFree(h->err);
-  h->err = nullptr;
-  h->errcap = 0;
-  if (int rc = dmalloc(&h->err, count)) return rc;
-  h->errcap = count;
-  return FU_OK;
-}
-
-int launch_err(fu_lossy *h, u64 *slot) {
-  const unsigned grid = (unsigned)std::min<i64>(1024, ((i64)h->n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(kl_max_err, dim3(grid), dim3(kBlock), 0, h->stream, h->n, h->a[(h->round + 1) & 1], h->target,
-                     slot);  // a of the last round run
-  HIP_TRY(hipGetLastError());
-  return FU_OK;
-}
-
-int launch_round(fu_lossy *h) {
+static int launch_round(fu_lossy *h) {
   const int64_t r = h->round;
   RoundArgs A;
   A.rowptr = h->rowptr;
@@ -324,35 +243,11 @@ int launch_round(fu_lossy *h) {
   return FU_OK;
 }
 
-// rev must pair every slot with its reverse slot: in range, an involution, and pointing into
-// the row of the slot's neighbour at a slot that points back. A rev that fails this would be an
-// out-of-bounds or wrong gather on the device.
-int check_rev(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev) {
-  for (int32_t i = 0; i < n; ++i)
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-      const int64_t r = rev[k];
-      if (r < 0 || r >= e || rev[r] != k || col[r] != i || r < rowptr[col[k]] || r >= rowptr[col[k] + 1])
-        return fail(FU_ERR_GRAPH, "fu_lossy_create: rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
-                                      std::to_string(k));
-    }
-  return FU_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int fu_lossy_destroy(fu_lossy *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_lossy_destroy: bad arguments");
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void *p : {(void *)h->rowptr, (void *)h->col, (void *)h->rev, (void *)h->hrows, (void *)h->tiles, (void *)h->down,
-                  (void *)h->v, (void *)h->target, (void *)h->a[0], (void *)h->a[1], (void *)h->f[0], (void *)h->f[1],
-                  (void *)h->lost, (void *)h->err})
-    if (p) (void)hipFree(p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (!h) return bad_arguments<fu_lossy>("destroy");
+  handle_close(h, {h->rowptr, h->col, h->rev, h->hrows, h->tiles, h->down, h->v, h->a[0], h->a[1], h->f[0], h->f[1], h->lost});
   delete h;
   return FU_OK;
 }
@@ -362,25 +257,15 @@ int fu_lossy_destroy(fu_lossy *h) {
 int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
                     const double *value, int32_t device, fu_lossy **out) {
   FU_TRY_BEGIN
-  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return fail(FU_ERR_ARG, "fu_lossy_create: bad arguments");
+  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_lossy>("create");
   if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_lossy_create: more than 2^31-1 directed edges (rev is int32)");
-  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, "fu_lossy_create: rowptr[0] must be 0 and rowptr[n] == e");
-  for (int32_t i = 0; i < n; ++i)
-    if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, "fu_lossy_create: rowptr not monotone");
-  for (int64_t q = 0; q < e; ++q)
-    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, "fu_lossy_create: col index out of range at edge " + std::to_string(q));
+  if (int rc = check_csr("fu_lossy_create", n, e, rowptr, col)) return rc;
   std::vector<int32_t> built;
   if (e > 0 && !rev) {
-    fu_graph g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + e);
-    if (int rc = fu::build_rev(g)) return rc;
-    built.swap(g.rev);
+    if (int rc = rev_of_csr(n, e, rowptr, col, &built)) return rc;
     rev = built.data();
   }
-  if (e > 0)
-    if (int rc = check_rev(n, e, rowptr, col, rev)) return rc;
+  if (int rc = check_rev("fu_lossy_create", RevCheck::kPairing, n, rowptr, col, rev)) return rc;
   // the launch plan: heavy rows one block each; the rows between them in tiles of at most
   // kTileRows rows and kTileEdges slots
   std::vector<int32_t> heavy;
@@ -395,58 +280,38 @@ int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
     tiles.push_back(make_int2(i, j));  // j > i: a light row alone always fits
     i = j;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, "fu_lossy_create: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, "fu_lossy_create: device out of range");
   auto *h = new fu_lossy();
-  h->device = device;
-  h->n = n;
-  h->E = e;
   h->n_tiles = (int32_t)tiles.size();
   h->n_heavy = (int32_t)heavy.size();
   auto cleanup = [&](int code) { fu_lossy_destroy(h); return code; };
   int rc = FU_OK;
-  if ((rc = set_device(h))) return cleanup(rc);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_lossy_create: hipStreamCreate failed"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_lossy_create: hipEventCreate failed"));
-  if ((rc = dmalloc(&h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(&h->col, e)) || (rc = dmalloc(&h->rev, e)) ||
-      (rc = dmalloc(&h->hrows, h->n_heavy)) || (rc = dmalloc(&h->tiles, h->n_tiles)) || (rc = dmalloc(&h->down, e)) ||
-      (rc = dmalloc(&h->v, n)) || (rc = dmalloc(&h->target, n)) || (rc = dmalloc(&h->a[0], n)) ||
-      (rc = dmalloc(&h->a[1], n)) || (rc = dmalloc(&h->f[0], e)) || (rc = dmalloc(&h->f[1], e)) ||
-      (rc = dmalloc(&h->lost, 1)) || (rc = err_slots(h, 1)))
+  if ((rc = handle_open(h, device, n, e, 1))) return cleanup(rc);
+  const int64_t e1 = std::max<int64_t>(e, 1);
+  if ((rc = dmalloc(h, &h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(h, &h->col, e)) || (rc = dmalloc(h, &h->rev, e)) ||
+      (rc = dmalloc(h, &h->hrows, h->n_heavy)) || (rc = dmalloc(h, &h->tiles, h->n_tiles)) ||
+      (rc = dmalloc(h, &h->down, e)) || (rc = dmalloc(h, &h->v, n)) || (rc = dmalloc(h, &h->a[0], n)) ||
+      (rc = dmalloc(h, &h->a[1], n)) || (rc = dmalloc(h, &h->f[0], e1)) || (rc = dmalloc(h, &h->f[1], e1)) ||
+      (rc = dmalloc(h, &h->lost, 1)))
     return cleanup(rc);
   static_assert(sizeof(i64) == sizeof(int64_t), "rowptr is uploaded as is");
-  if (hipMemcpy(h->rowptr, rowptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess ||
-      (e && hipMemcpy(h->col, col, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
-      (e && hipMemcpy(h->rev, rev, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
-      (h->n_heavy && hipMemcpy(h->hrows, heavy.data(), sizeof(int32_t) * heavy.size(), hipMemcpyHostToDevice) != hipSuccess) ||
-      (h->n_tiles && hipMemcpy(h->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(h->v, value, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_lossy_create: upload failed"));
-  if (hipMemset(h->a[0], 0, sizeof(double) * (size_t)n) != hipSuccess ||
-      hipMemset(h->a[1], 0, sizeof(double) * (size_t)n) != hipSuccess ||
-      hipMemset(h->f[0], 0, sizeof(double) * (size_t)std::max<int64_t>(e, 1)) != hipSuccess ||
-      hipMemset(h->f[1], 0, sizeof(double) * (size_t)std::max<int64_t>(e, 1)) != hipSuccess ||
-      hipMemset(h->lost, 0, sizeof(u64)) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_lossy_create: memset failed"));
+  if ((rc = put(h, h->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(h, h->col, col, e)) || (rc = put(h, h->rev, rev, e)) ||
+      (rc = put(h, h->hrows, heavy.data(), h->n_heavy)) || (rc = put(h, h->tiles, tiles.data(), h->n_tiles)) ||
+      (rc = put(h, h->v, value, n)))
+    return cleanup(rc);
+  if ((rc = zero(h, h->a[0], n)) || (rc = zero(h, h->a[1], n)) || (rc = zero(h, h->f[0], e1)) ||
+      (rc = zero(h, h->f[1], e1)) || (rc = zero(h, h->lost, 1)))
+    return cleanup(rc);
   *out = h;
   return FU_OK;
   FU_TRY_END
 }
 
 int fu_lossy_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_lossy **out) {
-  FU_TRY_BEGIN
-  if (!g || !value || !out) return fail(FU_ERR_ARG, "fu_lossy_create_from_graph: bad arguments");
-  const int64_t E = g->rowptr[g->n];
-  if ((int64_t)g->rev.size() != E) return fail(FU_ERR_GRAPH, "fu_lossy_create_from_graph: graph is not symmetric");
-  return fu_lossy_create(g->n, E, g->rowptr.data(), g->col.data(), E ? g->rev.data() : nullptr, value, device, out);
-  FU_TRY_END
+  return create_from_graph<fu_lossy>(g, value, out, [&](auto... csr) { return fu_lossy_create(csr..., value, device, out); });
 }
 
 int fu_lossy_set_loss(fu_lossy *h, double p, uint64_t seed) {
-  if (!h) return fail(FU_ERR_ARG, "fu_lossy_set_loss: bad arguments");
+  if (!h) return bad_arguments<fu_lossy>("set_loss");
   if (!(p >= 0.0 && p <= 1.0)) return fail(FU_ERR_ARG, "fu_lossy_set_loss: p must be in [0, 1]");
   h->p = p;  // kernel arguments of the rounds launched from now on
   h->seed = seed;
@@ -454,157 +319,62 @@ int fu_lossy_set_loss(fu_lossy *h, double p, uint64_t seed) {
 }
 
 int fu_lossy_set_link_mask(fu_lossy *h, const uint8_t *down) {
-  FU_TRY_BEGIN
-  if (!h) return fail(FU_ERR_ARG, "fu_lossy_set_link_mask: bad arguments");
+  if (!h) return bad_arguments<fu_lossy>("set_link_mask");
   if (!down || h->E == 0) {
     h->has_mask = false;  // rounds already queued keep their own argument copy; the buffer stays
     return FU_OK;
   }
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h->down, down, (size_t)h->E, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = upload(h, h->down, down, (size_t)h->E)) return rc;
   h->has_mask = true;
   return FU_OK;
-  FU_TRY_END
 }
 
 int fu_lossy_set_values(fu_lossy *h, const double *value) {
-  FU_TRY_BEGIN
-  if (!h || !value) return fail(FU_ERR_ARG, "fu_lossy_set_values: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h->v, value, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
-  FU_TRY_END
+  if (!h || !value) return bad_arguments<fu_lossy>("set_values");
+  return upload(h, h->v, value, sizeof(double) * (size_t)h->n);
 }
 
+// The flow and estimate buffers stay as they are: round 0 reads no state.
 int fu_lossy_reset(fu_lossy *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_lossy_reset: bad arguments");
+  if (!h) return bad_arguments<fu_lossy>("reset");
   if (int rc = set_device(h)) return rc;
   HIP_TRY(hipMemsetAsync(h->lost, 0, sizeof(u64), h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  h->round = 0;  // round 0 reads no state
+  h->round = 0;
   return FU_OK;
 }
 
-int fu_lossy_set_targets(fu_lossy *h, const double *target) {
-  FU_TRY_BEGIN
-  if (!h || !target) return fail(FU_ERR_ARG, "fu_lossy_set_targets: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h->target, target, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->has_target = true;
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_lossy_run(fu_lossy *h, int32_t rounds, int32_t err_every, double *err_trace) {
-  FU_TRY_BEGIN
-  if (!h || rounds < 0) return fail(FU_ERR_ARG, "fu_lossy_run: bad arguments");
-  if (err_every > 0 && !h->has_target) return fail(FU_ERR_STATE, "fu_lossy_run: err_every > 0 needs fu_lossy_set_targets");
-  if (int rc = set_device(h)) return rc;
-  const int64_t nerr = err_every > 0 ? rounds / err_every : 0;
-  if (nerr > 0) {
-    if (int rc = err_slots(h, nerr)) return rc;
-    HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64) * (size_t)nerr, h->stream));
-  }
-  for (int32_t r = 0; r < rounds; ++r) {
-    if (int rc = launch_round(h)) return rc;
-    if (nerr > 0 && (r + 1) % err_every == 0)
-      if (int rc = launch_err(h, h->err + ((r + 1) / err_every - 1))) return rc;
-  }
-  if (nerr > 0) {
-    std::vector<u64> bits((size_t)nerr);
-    HIP_TRY(hipMemcpyAsync(bits.data(), h->err, sizeof(u64) * bits.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (err_trace) std::memcpy(err_trace, bits.data(), sizeof(double) * bits.size());
-  }
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_lossy_run_timed(fu_lossy *h, int32_t rounds, float *ms) {
-  FU_TRY_BEGIN
-  if (!h || !ms || rounds < 0) return fail(FU_ERR_ARG, "fu_lossy_run_timed: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  for (int32_t r = 0; r < rounds; ++r)
-    if (int rc = launch_round(h)) return rc;
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(hipEventSynchronize(h->ev1));
-  HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_lossy_max_err(fu_lossy *h, double *out) {
-  FU_TRY_BEGIN
-  if (!h || !out) return fail(FU_ERR_ARG, "fu_lossy_max_err: bad arguments");
-  if (!h->has_target) return fail(FU_ERR_STATE, "fu_lossy_max_err: call fu_lossy_set_targets first");
-  if (h->round == 0) return fail(FU_ERR_STATE, "fu_lossy_max_err: no round has run");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64), h->stream));
-  if (int rc = launch_err(h, h->err)) return rc;
-  u64 bits = 0;
-  HIP_TRY(hipMemcpyAsync(&bits, h->err, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  std::memcpy(out, &bits, sizeof(double));
-  return FU_OK;
-  FU_TRY_END
-}
+int fu_lossy_set_targets(fu_lossy *h, const double *target) { return set_targets(h, target); }
+int fu_lossy_run(fu_lossy *h, int32_t rounds, int32_t err_every, double *err_trace) { return run(h, rounds, err_every, err_trace); }
+int fu_lossy_run_timed(fu_lossy *h, int32_t rounds, float *ms) { return run_timed(h, rounds, ms); }
+int fu_lossy_max_err(fu_lossy *h, double *out) { return max_err(h, out, /*needs_a_round=*/true); }
+int fu_lossy_get_round(fu_lossy *h, int64_t *rounds_done) { return get_round(h, rounds_done); }
+int fu_lossy_synchronize(fu_lossy *h) { return synchronize(h); }
 
 int fu_lossy_get_estimates(fu_lossy *h, double *a_out) {
-  FU_TRY_BEGIN
-  if (!h || !a_out) return fail(FU_ERR_ARG, "fu_lossy_get_estimates: bad arguments");
+  if (!h || !a_out) return bad_arguments<fu_lossy>("get_estimates");
   if (h->round == 0) {  // zero state
     std::fill(a_out, a_out + h->n, 0.0);
     return FU_OK;
   }
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(a_out, h->a[(h->round + 1) & 1], sizeof(double) * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
-  FU_TRY_END
+  return download(h, a_out, h->a[(h->round + 1) & 1], sizeof(double) * (size_t)h->n);
 }
 
 int fu_lossy_get_flows(fu_lossy *h, double *f_out) {
-  FU_TRY_BEGIN
-  if (!h || (!f_out && h->E)) return fail(FU_ERR_ARG, "fu_lossy_get_flows: bad arguments");
-  if (h->E == 0) return FU_OK;
+  if (!h || (!f_out && h->E)) return bad_arguments<fu_lossy>("get_flows");
   if (h->round == 0) {  // zero state
     std::fill(f_out, f_out + h->E, 0.0);
     return FU_OK;
   }
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(f_out, h->f[(h->round + 1) & 1], sizeof(double) * (size_t)h->E, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_lossy_get_round(fu_lossy *h, int64_t *rounds_done) {
-  if (!h || !rounds_done) return fail(FU_ERR_ARG, "fu_lossy_get_round: bad arguments");
-  *rounds_done = h->round;
-  return FU_OK;
+  return download(h, f_out, h->f[(h->round + 1) & 1], sizeof(double) * (size_t)h->E);
 }
 
 int fu_lossy_get_stats(fu_lossy *h, int64_t out[2]) {
-  FU_TRY_BEGIN
-  if (!h || !out) return fail(FU_ERR_ARG, "fu_lossy_get_stats: bad arguments");
-  if (int rc = set_device(h)) return rc;
+  if (!h || !out) return bad_arguments<fu_lossy>("get_stats");
   u64 lost = 0;
-  HIP_TRY(hipMemcpyAsync(&lost, h->lost, sizeof(lost), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = download(h, &lost, h->lost, sizeof(lost))) return rc;
   out[0] = h->round > 1 ? h->E * (h->round - 1) : 0;  // round 0 offers nothing
   out[1] = (int64_t)lost;
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_lossy_synchronize(fu_lossy *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_lossy_synchronize: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
   return FU_OK;
 }
 

@@ -23,23 +23,12 @@
 // its matched listeners, 8 lanes per pair load both flow rows into LDS, one lane carries the
 // two chains), then kp_heavy for the pairs with a row above kLightDeg (one block per pair, the
 // rows in LDS chunks, thread 0 carrying). Nothing in a round waits for the host.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "fu_common.h"
+//
+// The handle scaffold (create and destroy, the run loops, the error slots and k_max_err, the
+// small entry points) is csrc/fu_handle.h, shared with the batched and lossy engines.
+#include "fu_handle.h"
 
 using namespace fu;
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 namespace {
 
@@ -50,7 +39,6 @@ constexpr int kLightDeg = 64;               // a pair with a row above this degr
 constexpr int kChunk = 1024;                // kp_heavy: flows staged in LDS per chunk
 constexpr int kHeavyBlocks = 1024;          // kp_heavy: at most this many blocks share the round's heavy pairs
 
-using u64 = unsigned long long;
 constexpr u64 kNone = ~0ull;  // a listener's word without a proposal (no key is all-ones: i < 2^31)
 
 static_assert(sizeof(u64) == sizeof(uint64_t), "the words are read as uint64_t on the host");
@@ -259,114 +247,36 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
   }
 }
 
-// max_i |last_i - target_i| as a uint64 bit pattern, the rule of the other engines: non-negative
-// doubles order like their bits, and a NaN with its sign cleared is above +inf.
-__global__ __launch_bounds__(kBlock) void kp_max_err(int n, const double *__restrict__ a,
-                                                     const double *__restrict__ target, u64 *__restrict__ err) {
-  u64 m = 0;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const u64 x = (u64)__double_as_longlong(fabs(a[i] - target[i]));
-    m = x > m ? x : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 y = __shfl_xor(m, off, 64);
-    m = m > y ? m : y;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
-}
-
 // How many nodes have never fired: one atomic per block that found some.
 __global__ __launch_bounds__(kBlock) void kp_count_unfired(int n, const unsigned char *__restrict__ fired,
                                                            u64 *__restrict__ out) {
   int cnt = 0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) cnt += fired[i] == 0;
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-  __shared__ int s_w[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int q = 0; q < kBlock / 64; ++q) t += s_w[q];
-    if (t) atomicAdd(out, (u64)t);
-  }
+  block_count_to<kBlock>(cnt, out);
 }
 
 }  // namespace
 
-struct fu_pair {
-  int device = 0;
-  int32_t n = 0;
-  int64_t E = 0;
-  int64_t round = 0;
+struct fu_pair : handle_base {
+  static constexpr const char *kTag = "fu_pair";
   uint64_t seed = 0;
-  int match = 0;  // 0: kp_propose, 1: kp_scan
-  bool has_target = false;
+  int match = 0;             // 0: kp_propose, 1: kp_scan
   int32_t n_heavy_rows = 0;  // rows above kLightDeg: the bound on a round's heavy pairs
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int64_t *rowptr = nullptr;
   int32_t *col = nullptr, *rev = nullptr;
-  double *v = nullptr, *target = nullptr, *f = nullptr, *c = nullptr, *last = nullptr;
+  double *v = nullptr, *f = nullptr, *c = nullptr, *last = nullptr;
   u64 *word = nullptr;
   unsigned char *fired = nullptr;
   int2 *heavy = nullptr;
   unsigned *n_heavy = nullptr;
   u64 *stat = nullptr;  // [0] pairs exchanged, [1] scratch of kp_count_unfired
-  u64 *err = nullptr;
-  int64_t errcap = 0;
 };
 
-namespace {
+static unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
 
-template <typename T>
-int dmalloc(T **p, int64_t count) {
-  if (hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
-    *p = nullptr;
-    return fail(FU_ERR_ALLOC, "fu_pair: hipMalloc failed");
-  }
-  return FU_OK;
-}
+static int launch_err(fu_pair *h, u64 *slot) { return launch_max_err<kBlock>(h, h->last, slot); }
 
-int set_device(fu_pair *h) {
-  HIP_TRY(hipSetDevice(h->device));
-  return FU_OK;
-}
-
-int err_slots(fu_pair *h, int64_t count) {
-  if (count <= h->errcap) return FU_OK;
-  if (h->err) hipFree(h->err);
-  h->err = nullptr;
-  h->errcap = 0;
-  if (int rc = dmalloc(&h->err, count)) return rc;
-  h->errcap = count;
-  return FU_OK;
-}
-
-unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
-
-int launch_err(fu_pair *h, u64 *slot) {
-  hipLaunchKernelGGL(kp_max_err, dim3(std::min(1024u, node_grid(h))), dim3(kBlock), 0, h->stream, h->n, h->last,
-                     h->target, slot);
-  HIP_TRY(hipGetLastError());
-  return FU_OK;
-}
-
-// Zero state: flows, caches, last averages, fired flags, counters; every word without a proposal.
-int zero_state(fu_pair *h) {
-  const size_t e = (size_t)std::max<int64_t>(h->E, 1), n = (size_t)h->n;
-  HIP_TRY(hipMemsetAsync(h->f, 0, sizeof(double) * e, h->stream));
-  HIP_TRY(hipMemsetAsync(h->c, 0, sizeof(double) * e, h->stream));
-  HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n, h->stream));
-  HIP_TRY(hipMemsetAsync(h->fired, 0, n, h->stream));
-  HIP_TRY(hipMemsetAsync(h->word, 0xFF, sizeof(u64) * n, h->stream));
-  HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * 2, h->stream));
-  HIP_TRY(hipMemsetAsync(h->n_heavy, 0, sizeof(unsigned), h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->round = 0;
-  return FU_OK;
-}
-
-int launch_round(fu_pair *h) {
+static int launch_round(fu_pair *h) {
   RoundArgs A;
   A.n = h->n;
   A.rowptr = h->rowptr;
@@ -398,44 +308,26 @@ int launch_round(fu_pair *h) {
   return FU_OK;
 }
 
-int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col) {
-  const std::string w(who);
-  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, w + ": rowptr[0] must be 0 and rowptr[n] == e");
-  for (int32_t i = 0; i < n; ++i)
-    if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, w + ": rowptr not monotone");
-  for (int64_t q = 0; q < e; ++q)
-    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, w + ": col index out of range at edge " + std::to_string(q));
+// Zero state: flows, caches, last averages, fired flags, counters; every word without a proposal.
+static int zero_state(fu_pair *h) {
+  const size_t e = (size_t)std::max<int64_t>(h->E, 1), n = (size_t)h->n;
+  HIP_TRY(hipMemsetAsync(h->f, 0, sizeof(double) * e, h->stream));
+  HIP_TRY(hipMemsetAsync(h->c, 0, sizeof(double) * e, h->stream));
+  HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->fired, 0, n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->word, 0xFF, sizeof(u64) * n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * 2, h->stream));
+  HIP_TRY(hipMemsetAsync(h->n_heavy, 0, sizeof(unsigned), h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->round = 0;
   return FU_OK;
 }
-
-// rev must pair every slot with its reverse slot, as in fu_lossy_create: a rev that fails this
-// would be an out-of-bounds or wrong access on the device.
-int check_rev(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev) {
-  for (int32_t i = 0; i < n; ++i)
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-      const int64_t r = rev[k];
-      if (r < 0 || r >= e || rev[r] != k || col[r] != i || r < rowptr[col[k]] || r >= rowptr[col[k] + 1])
-        return fail(FU_ERR_GRAPH, "fu_pair_create: rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
-                                      std::to_string(k));
-    }
-  return FU_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
 int fu_pair_destroy(fu_pair *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_pair_destroy: bad arguments");
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void *p : {(void *)h->rowptr, (void *)h->col, (void *)h->rev, (void *)h->v, (void *)h->target, (void *)h->f,
-                  (void *)h->c, (void *)h->last, (void *)h->word, (void *)h->fired, (void *)h->heavy, (void *)h->n_heavy,
-                  (void *)h->stat, (void *)h->err})
-    if (p) (void)hipFree(p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (!h) return bad_arguments<fu_pair>("destroy");
+  handle_close(h, {h->rowptr, h->col, h->rev, h->v, h->f, h->c, h->last, h->word, h->fired, h->heavy, h->n_heavy, h->stat});
   delete h;
   return FU_OK;
 }
@@ -445,72 +337,47 @@ int fu_pair_destroy(fu_pair *h) {
 int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
                    const double *value, int32_t device, fu_pair **out) {
   FU_TRY_BEGIN
-  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return fail(FU_ERR_ARG, "fu_pair_create: bad arguments");
+  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_pair>("create");
   if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_pair_create: more than 2^31-1 directed edges (rev is int32)");
   if (int rc = check_csr("fu_pair_create", n, e, rowptr, col)) return rc;
   std::vector<int32_t> built;
   if (e > 0 && !rev) {
-    fu_graph g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + e);
-    if (int rc = fu::build_rev(g)) return rc;
-    built.swap(g.rev);
+    if (int rc = rev_of_csr(n, e, rowptr, col, &built)) return rc;
     rev = built.data();
   }
-  if (e > 0)
-    if (int rc = check_rev(n, e, rowptr, col, rev)) return rc;
+  if (int rc = check_rev("fu_pair_create", RevCheck::kPairing, n, rowptr, col, rev)) return rc;
   int32_t heavy_rows = 0;
   for (int32_t i = 0; i < n; ++i) heavy_rows += rowptr[i + 1] - rowptr[i] > kLightDeg;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, "fu_pair_create: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, "fu_pair_create: device out of range");
   auto *h = new fu_pair();
-  h->device = device;
-  h->n = n;
-  h->E = e;
   h->n_heavy_rows = heavy_rows;
   auto cleanup = [&](int code) { fu_pair_destroy(h); return code; };
   int rc = FU_OK;
-  if ((rc = set_device(h))) return cleanup(rc);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: hipStreamCreate failed"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: hipEventCreate failed"));
-  if ((rc = dmalloc(&h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(&h->col, e)) || (rc = dmalloc(&h->rev, e)) ||
-      (rc = dmalloc(&h->v, n)) || (rc = dmalloc(&h->target, n)) || (rc = dmalloc(&h->f, e)) || (rc = dmalloc(&h->c, e)) ||
-      (rc = dmalloc(&h->last, n)) || (rc = dmalloc(&h->word, n)) || (rc = dmalloc(&h->fired, n)) ||
-      (rc = dmalloc(&h->heavy, heavy_rows)) || (rc = dmalloc(&h->n_heavy, 1)) || (rc = dmalloc(&h->stat, 2)) ||
-      (rc = err_slots(h, 1)))
+  if ((rc = handle_open(h, device, n, e, 1))) return cleanup(rc);
+  if ((rc = dmalloc(h, &h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(h, &h->col, e)) || (rc = dmalloc(h, &h->rev, e)) ||
+      (rc = dmalloc(h, &h->v, n)) || (rc = dmalloc(h, &h->f, e)) || (rc = dmalloc(h, &h->c, e)) ||
+      (rc = dmalloc(h, &h->last, n)) || (rc = dmalloc(h, &h->word, n)) || (rc = dmalloc(h, &h->fired, n)) ||
+      (rc = dmalloc(h, &h->heavy, heavy_rows)) || (rc = dmalloc(h, &h->n_heavy, 1)) || (rc = dmalloc(h, &h->stat, 2)))
     return cleanup(rc);
-  if (hipMemcpy(h->rowptr, rowptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess ||
-      (e && hipMemcpy(h->col, col, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
-      (e && hipMemcpy(h->rev, rev, sizeof(int32_t) * (size_t)e, hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(h->v, value, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(FU_ERR_HIP, "fu_pair_create: upload failed"));
-  if ((rc = zero_state(h))) return cleanup(rc);
+  if ((rc = put(h, h->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(h, h->col, col, e)) || (rc = put(h, h->rev, rev, e)) ||
+      (rc = put(h, h->v, value, n)) || (rc = zero_state(h)))
+    return cleanup(rc);
   *out = h;
   return FU_OK;
   FU_TRY_END
 }
 
 int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_pair **out) {
-  FU_TRY_BEGIN
-  if (!g || !value || !out) return fail(FU_ERR_ARG, "fu_pair_create_from_graph: bad arguments");
-  const int64_t E = g->rowptr[g->n];
-  if ((int64_t)g->rev.size() != E) return fail(FU_ERR_GRAPH, "fu_pair_create_from_graph: graph is not symmetric");
-  return fu_pair_create(g->n, E, g->rowptr.data(), g->col.data(), E ? g->rev.data() : nullptr, value, device, out);
-  FU_TRY_END
+  return create_from_graph<fu_pair>(g, value, out, [&](auto... csr) { return fu_pair_create(csr..., value, device, out); });
 }
 
 int fu_pair_set_seed(fu_pair *h, uint64_t seed) {
-  if (!h) return fail(FU_ERR_ARG, "fu_pair_set_seed: bad arguments");
+  if (!h) return bad_arguments<fu_pair>("set_seed");
   h->seed = seed;  // a kernel argument of the rounds launched from now on
   return FU_OK;
 }
 
 int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
-  if (!h || !key) return fail(FU_ERR_ARG, "fu_pair_set_option: bad arguments");
+  if (!h || !key) return bad_arguments<fu_pair>("set_option");
   if (std::strcmp(key, "match") == 0 && (value == 0 || value == 1)) {
     h->match = (int)value;
     return FU_OK;
@@ -519,137 +386,54 @@ int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
 }
 
 int fu_pair_set_values(fu_pair *h, const double *value) {
-  FU_TRY_BEGIN
-  if (!h || !value) return fail(FU_ERR_ARG, "fu_pair_set_values: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h->v, value, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
-  FU_TRY_END
+  if (!h || !value) return bad_arguments<fu_pair>("set_values");
+  return upload(h, h->v, value, sizeof(double) * (size_t)h->n);
 }
 
 int fu_pair_reset(fu_pair *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_pair_reset: bad arguments");
+  if (!h) return bad_arguments<fu_pair>("reset");
   if (int rc = set_device(h)) return rc;
   return zero_state(h);
 }
 
-int fu_pair_set_targets(fu_pair *h, const double *target) {
-  FU_TRY_BEGIN
-  if (!h || !target) return fail(FU_ERR_ARG, "fu_pair_set_targets: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(h->target, target, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->has_target = true;
-  return FU_OK;
-  FU_TRY_END
-}
+int fu_pair_set_targets(fu_pair *h, const double *target) { return set_targets(h, target); }
+int fu_pair_run(fu_pair *h, int32_t rounds, int32_t err_every, double *err_trace) { return run(h, rounds, err_every, err_trace); }
+int fu_pair_run_timed(fu_pair *h, int32_t rounds, float *ms) { return run_timed(h, rounds, ms); }
+// Allowed before any round: every node's last average is 0.0 then.
+int fu_pair_max_err(fu_pair *h, double *out) { return max_err(h, out, /*needs_a_round=*/false); }
+int fu_pair_get_round(fu_pair *h, int64_t *rounds_done) { return get_round(h, rounds_done); }
+int fu_pair_synchronize(fu_pair *h) { return synchronize(h); }
 
-int fu_pair_run(fu_pair *h, int32_t rounds, int32_t err_every, double *err_trace) {
-  FU_TRY_BEGIN
-  if (!h || rounds < 0) return fail(FU_ERR_ARG, "fu_pair_run: bad arguments");
-  if (err_every > 0 && !h->has_target) return fail(FU_ERR_STATE, "fu_pair_run: err_every > 0 needs fu_pair_set_targets");
-  if (int rc = set_device(h)) return rc;
-  const int64_t nerr = err_every > 0 ? rounds / err_every : 0;
-  if (nerr > 0) {
-    if (int rc = err_slots(h, nerr)) return rc;
-    HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64) * (size_t)nerr, h->stream));
-  }
-  for (int32_t r = 0; r < rounds; ++r) {
-    if (int rc = launch_round(h)) return rc;
-    if (nerr > 0 && (r + 1) % err_every == 0)
-      if (int rc = launch_err(h, h->err + ((r + 1) / err_every - 1))) return rc;
-  }
-  if (nerr > 0) {
-    std::vector<u64> bits((size_t)nerr);
-    HIP_TRY(hipMemcpyAsync(bits.data(), h->err, sizeof(u64) * bits.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (err_trace) std::memcpy(err_trace, bits.data(), sizeof(double) * bits.size());
-  }
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_pair_run_timed(fu_pair *h, int32_t rounds, float *ms) {
-  FU_TRY_BEGIN
-  if (!h || !ms || rounds < 0) return fail(FU_ERR_ARG, "fu_pair_run_timed: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  for (int32_t r = 0; r < rounds; ++r)
-    if (int rc = launch_round(h)) return rc;
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(hipEventSynchronize(h->ev1));
-  HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
-  return FU_OK;
-  FU_TRY_END
-}
-
-int fu_pair_max_err(fu_pair *h, double *out) {
-  FU_TRY_BEGIN
-  if (!h || !out) return fail(FU_ERR_ARG, "fu_pair_max_err: bad arguments");
-  if (!h->has_target) return fail(FU_ERR_STATE, "fu_pair_max_err: call fu_pair_set_targets first");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemsetAsync(h->err, 0, sizeof(u64), h->stream));
-  if (int rc = launch_err(h, h->err)) return rc;
-  u64 bits = 0;
-  HIP_TRY(hipMemcpyAsync(&bits, h->err, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  std::memcpy(out, &bits, sizeof(double));
-  return FU_OK;
-  FU_TRY_END
-}
-
-static int download(fu_pair *h, void *dst, const void *src, size_t bytes) {
-  if (bytes == 0) return FU_OK;
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
-}
-
+// The state is on the device from create on: round 0 downloads like any other.
 int fu_pair_get_estimates(fu_pair *h, double *last_out) {
-  if (!h || !last_out) return fail(FU_ERR_ARG, "fu_pair_get_estimates: bad arguments");
+  if (!h || !last_out) return bad_arguments<fu_pair>("get_estimates");
   return download(h, last_out, h->last, sizeof(double) * (size_t)h->n);
 }
 
 int fu_pair_get_flows(fu_pair *h, double *f_out) {
-  if (!h || (!f_out && h->E)) return fail(FU_ERR_ARG, "fu_pair_get_flows: bad arguments");
+  if (!h || (!f_out && h->E)) return bad_arguments<fu_pair>("get_flows");
   return download(h, f_out, h->f, sizeof(double) * (size_t)h->E);
 }
 
 int fu_pair_get_cache(fu_pair *h, double *c_out) {
-  if (!h || (!c_out && h->E)) return fail(FU_ERR_ARG, "fu_pair_get_cache: bad arguments");
+  if (!h || (!c_out && h->E)) return bad_arguments<fu_pair>("get_cache");
   return download(h, c_out, h->c, sizeof(double) * (size_t)h->E);
-}
-
-int fu_pair_get_round(fu_pair *h, int64_t *rounds_done) {
-  if (!h || !rounds_done) return fail(FU_ERR_ARG, "fu_pair_get_round: bad arguments");
-  *rounds_done = h->round;
-  return FU_OK;
 }
 
 int fu_pair_get_stats(fu_pair *h, int64_t out[2]) {
   FU_TRY_BEGIN
-  if (!h || !out) return fail(FU_ERR_ARG, "fu_pair_get_stats: bad arguments");
+  if (!h || !out) return bad_arguments<fu_pair>("get_stats");
   if (int rc = set_device(h)) return rc;
   HIP_TRY(hipMemsetAsync(h->stat + 1, 0, sizeof(u64), h->stream));
   hipLaunchKernelGGL(kp_count_unfired, dim3(std::min(1024u, node_grid(h))), dim3(kBlock), 0, h->stream, h->n, h->fired,
                      h->stat + 1);
   HIP_TRY(hipGetLastError());
   u64 s[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(s, h->stat, sizeof(s), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = download(h, s, h->stat, sizeof(s))) return rc;
   out[0] = (int64_t)s[0];
   out[1] = (int64_t)s[1];
   return FU_OK;
   FU_TRY_END
-}
-
-int fu_pair_synchronize(fu_pair *h) {
-  if (!h) return fail(FU_ERR_ARG, "fu_pair_synchronize: bad arguments");
-  if (int rc = set_device(h)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return FU_OK;
 }
 
 int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed, int64_t round, int32_t *mate,

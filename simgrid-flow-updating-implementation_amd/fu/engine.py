@@ -57,13 +57,144 @@ def _cand_name(code: int) -> str:
     return "recon" + {3: "_512", 1: "_1024", 2: "_1024x256"}.get(geo, "")
 
 
-class CollectAll:
+_OPS = ("create", "create_from_graph", "destroy", "reset", "set_targets", "set_values", "run", "run_timed", "max_err",
+        "get_estimates", "get_flows", "get_round", "get_stats", "synchronize")
+
+
+def _c_names(prefix: str, **irregular) -> dict:
+    """Operation -> C entry point: prefix + operation, but for the names given."""
+    return {**{op: prefix + op for op in _OPS}, **irregular}
+
+
+class _Handle:
+    """What the round engines share on the Python side: one device handle `_h` behind the C
+    entry points named in `_C`, n nodes, E slots and `_cols` values per node (None: one, and
+    arrays of shape (n,); K: arrays of shape (n, K))."""
+
+    _C: dict = {}
+    _cols = None
+    _NDIM = 1
+    _ROWS = "len(values)"  # how the class's messages call the number of value rows
+    _REV_LEN_CHECKED = True
+
+    def _call(self, op: str, *args):
+        return L.call(self._C[op], self._h, *args)
+
+    def _shape(self, rows: int) -> tuple:
+        return (rows,) if self._cols is None else (rows, self._cols)
+
+    def _open(self, graph, values, rowptr, col, rev, device, extra=lambda v: ()):
+        """The handle from a Graph or a raw CSR; extra(values) goes in front of the values in
+        the C call (the batch's K)."""
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim != self._NDIM:
+            raise ValueError(f"values must have shape {'(n,)' if self._NDIM == 1 else '(n, K)'}, got {v.shape}")
+        self.values = np.ascontiguousarray(v)
+        extra = extra(v)
+        out = L.vp()
+        if graph is not None:
+            if v.shape[0] != graph.n:
+                raise ValueError(f"{self._ROWS} != graph.n")
+            L.call(self._C["create_from_graph"], graph._h, *extra, L.ptr(self.values), int(device), ctypes.byref(out))
+            self.n, self.E = graph.n, graph.E
+        else:
+            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+            c = np.ascontiguousarray(col, dtype=np.int32)
+            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
+            n = len(rp) - 1
+            if v.shape[0] != n:
+                raise ValueError(f"{self._ROWS} != n")
+            if self._REV_LEN_CHECKED and r is not None and len(r) != len(c):
+                raise ValueError("len(rev) != len(col)")
+            L.call(self._C["create"], n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), *extra, L.ptr(self.values),
+                   int(device), ctypes.byref(out))
+            self.n, self.E = n, int(rp[-1])
+        self._h = out
+
+    def reset(self):
+        self._call("reset")
+
+    def set_targets(self, target):
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        if t.shape != self._shape(self.n):
+            raise ValueError(f"targets must have shape {self._shape(self.n)}, got {t.shape}")
+        self._call("set_targets", L.ptr(t))
+
+    def _set_values(self, values):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.shape != self._shape(self.n):
+            raise ValueError(f"values must have shape {self._shape(self.n)}, got {v.shape}")
+        self._call("set_values", L.ptr(v))
+        self.values = v
+
+    def run(self, rounds: int, err_every: int = 0):
+        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
+        if err_every > 0:
+            trace = np.empty(self._shape(max(rounds // err_every, 1)))
+            self._call("run", int(rounds), int(err_every), L.ptr(trace))
+            return trace[:rounds // err_every]
+        self._call("run", int(rounds), 0, None)
+        return None
+
+    def run_timed(self, rounds: int) -> float:
+        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
+        ms = L.f32()
+        self._call("run_timed", int(rounds), ctypes.byref(ms))
+        return float(ms.value)
+
+    def max_err(self):
+        out = np.empty(self._cols or 1)
+        self._call("max_err", out.ctypes.data_as(L.P(L.f64)))
+        return out if self._cols else float(out[0])
+
+    def estimates(self) -> np.ndarray:
+        a = np.empty(self._shape(self.n))
+        self._call("get_estimates", L.ptr(a))
+        return a
+
+    def flows(self) -> np.ndarray:
+        f = np.empty(self._shape(max(self.E, 1)))
+        self._call("get_flows", L.ptr(f))
+        return f[:self.E]
+
+    @property
+    def rounds_done(self) -> int:
+        r = L.i64()
+        self._call("get_round", ctypes.byref(r))
+        return int(r.value)
+
+    def _stats(self) -> tuple:
+        s = np.zeros(2, dtype=np.int64)
+        self._call("get_stats", L.ptr(s))
+        return int(s[0]), int(s[1])
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(L.lib, self._C["destroy"])(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class CollectAll(_Handle):
     """Synchronous collect-all engine on one GPU.
 
     >>> g = Graph.erdos_renyi(1_000_000, 4_000_000, seed=1)
     >>> eng = CollectAll(g, uniform_values(g.n, seed=0))
     >>> eng.run(1000); est = eng.estimates()
     """
+
+    _C = _c_names("fu_", run="fu_run_collectall", run_timed="fu_run_collectall_timed")
 
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None,
                  rev=None, device: int = 0, kernel: str | int = "auto",
@@ -101,27 +232,9 @@ class CollectAll:
     def set_option(self, key: str, value: int):
         L.call("fu_set_option", self._h, key.encode(), int(value))
 
-    def reset(self):
-        L.call("fu_reset", self._h)
-
     def set_targets(self, target):
         self._target = np.ascontiguousarray(target, dtype=np.float64)
         L.call("fu_set_targets", self._h, L.ptr(self._target))
-
-    def run(self, rounds: int, err_every: int = 0):
-        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
-        if err_every > 0:
-            trace = np.empty(max(rounds // err_every, 1))
-            L.call("fu_run_collectall", self._h, int(rounds), int(err_every), L.ptr(trace))
-            return trace[:rounds // err_every]
-        L.call("fu_run_collectall", self._h, int(rounds), 0, None)
-        return None
-
-    def run_timed(self, rounds: int) -> float:
-        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
-        ms = L.f32()
-        L.call("fu_run_collectall_timed", self._h, int(rounds), ctypes.byref(ms))
-        return float(ms.value)
 
     def tune(self):
         """One autotune pass now (kernel "auto"), outside any timed region: ~55 real rounds
@@ -145,21 +258,6 @@ class CollectAll:
         L.call("fu_mark_elapsed", self._h, int(a), int(b), ctypes.byref(ms))
         return float(ms.value)
 
-    def max_err(self) -> float:
-        out = L.f64()
-        L.call("fu_max_err", self._h, ctypes.byref(out))
-        return float(out.value)
-
-    def estimates(self) -> np.ndarray:
-        a = np.empty(self.n)
-        L.call("fu_get_estimates", self._h, L.ptr(a))
-        return a
-
-    def flows(self) -> np.ndarray:
-        f = np.empty(max(self.E, 1))
-        L.call("fu_get_flows", self._h, L.ptr(f))
-        return f[:self.E]
-
     def info(self) -> dict:
         """Kernel in use (after autotuning), autotune state, rounds done."""
         return handle_info(self._h)
@@ -171,31 +269,8 @@ class CollectAll:
         L.call("fu_get_pack", self._h, L.ptr(w))
         return tuple(int(x) for x in w)
 
-    @property
-    def rounds_done(self) -> int:
-        r = L.i64()
-        L.call("fu_get_round", self._h, ctypes.byref(r))
-        return int(r.value)
 
-    def synchronize(self):
-        L.call("fu_synchronize", self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib.fu_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class CollectAllBatch:
+class CollectAllBatch(_Handle):
     """K value columns over one graph in one pass per round (fu_batch_*): each column is an
     independent run of `CollectAll`, bit for bit. `values` has shape (n, K), 1 <= K <= 16.
 
@@ -204,95 +279,20 @@ class CollectAllBatch:
     >>> avg, inv_n = eng.estimates()[0]; total = avg / inv_n    # AVG, COUNT = 1 / inv_n, SUM
     """
 
+    _C = _c_names("fu_batch_")
+    _NDIM = 2
+    _ROWS = "values.shape[0]"
+    _REV_LEN_CHECKED = False  # fu_batch_create proves symmetry with rev and never uploads it
+
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None,
                  rev=None, device: int = 0):
-        v = np.asarray(values, dtype=np.float64)
-        if v.ndim != 2:
-            raise ValueError(f"values must have shape (n, K), got {v.shape}")
-        self.values = np.ascontiguousarray(v)
-        k = int(v.shape[1])
-        out = L.vp()
-        if graph is not None:
-            if v.shape[0] != graph.n:
-                raise ValueError("values.shape[0] != graph.n")
-            L.call("fu_batch_create_from_graph", graph._h, k, L.ptr(self.values), int(device),
-                   ctypes.byref(out))
-            self.n, self.E = graph.n, graph.E
-        else:
-            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
-            c = np.ascontiguousarray(col, dtype=np.int32)
-            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
-            n = len(rp) - 1
-            if v.shape[0] != n:
-                raise ValueError("values.shape[0] != n")
-            L.call("fu_batch_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), k,
-                   L.ptr(self.values), int(device), ctypes.byref(out))
-            self.n, self.E = n, int(rp[-1])
-        self.K = k
-        self._h = out
-
-    def reset(self):
-        L.call("fu_batch_reset", self._h)
-
-    def set_targets(self, target):
-        t = np.ascontiguousarray(target, dtype=np.float64)
-        if t.shape != (self.n, self.K):
-            raise ValueError(f"targets must have shape ({self.n}, {self.K}), got {t.shape}")
-        L.call("fu_batch_set_targets", self._h, L.ptr(t))
+        self._open(graph, values, rowptr, col, rev, device, extra=lambda v: (int(v.shape[1]),))
+        self.K = self._cols = int(self.values.shape[1])
 
     def run(self, rounds: int, err_every: int = 0):
         """Run `rounds` rounds; with err_every > 0 returns the (rounds // err_every, K)
         max-error trace, one row per check and one entry per column."""
-        if err_every > 0:
-            trace = np.empty((max(rounds // err_every, 1), self.K))
-            L.call("fu_batch_run", self._h, int(rounds), int(err_every), L.ptr(trace))
-            return trace[:rounds // err_every]
-        L.call("fu_batch_run", self._h, int(rounds), 0, None)
-        return None
-
-    def run_timed(self, rounds: int) -> float:
-        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
-        ms = L.f32()
-        L.call("fu_batch_run_timed", self._h, int(rounds), ctypes.byref(ms))
-        return float(ms.value)
-
-    def max_err(self) -> np.ndarray:
-        out = np.empty(self.K)
-        L.call("fu_batch_max_err", self._h, L.ptr(out))
-        return out
-
-    def estimates(self) -> np.ndarray:
-        a = np.empty((self.n, self.K))
-        L.call("fu_batch_get_estimates", self._h, L.ptr(a))
-        return a
-
-    def flows(self) -> np.ndarray:
-        f = np.empty((max(self.E, 1), self.K))
-        L.call("fu_batch_get_flows", self._h, L.ptr(f))
-        return f[:self.E]
-
-    @property
-    def rounds_done(self) -> int:
-        r = L.i64()
-        L.call("fu_batch_get_round", self._h, ctypes.byref(r))
-        return int(r.value)
-
-    def synchronize(self):
-        L.call("fu_batch_synchronize", self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib.fu_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return super().run(rounds, err_every)
 
 
 def lossy_delivered(seed: int, round: int, first: int, count: int, p: float) -> np.ndarray:
@@ -303,7 +303,7 @@ def lossy_delivered(seed: int, round: int, first: int, count: int, p: float) -> 
     return out[:int(count)]
 
 
-class CollectAllLossy:
+class CollectAllLossy(_Handle):
     """Synchronous collect-all rounds under message loss (fu_lossy_*): in every round >= 1 each
     message is lost with probability `loss` (a pure function of seed, round and slot) or by a
     link mask; the receiver then fires on the flow and estimate it stored itself (CA:87-91,
@@ -313,31 +313,11 @@ class CollectAllLossy:
     >>> eng.run(200); est = eng.estimates(); offered, lost = eng.stats
     """
 
+    _C = _c_names("fu_lossy_")
+
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
                  loss: float = 0.0, seed: int = 0, device: int = 0):
-        v = np.asarray(values, dtype=np.float64)
-        if v.ndim != 1:
-            raise ValueError(f"values must have shape (n,), got {v.shape}")
-        self.values = np.ascontiguousarray(v)
-        out = L.vp()
-        if graph is not None:
-            if len(v) != graph.n:
-                raise ValueError("len(values) != graph.n")
-            L.call("fu_lossy_create_from_graph", graph._h, L.ptr(self.values), int(device), ctypes.byref(out))
-            self.n, self.E = graph.n, graph.E
-        else:
-            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
-            c = np.ascontiguousarray(col, dtype=np.int32)
-            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
-            n = len(rp) - 1
-            if len(v) != n:
-                raise ValueError("len(values) != n")
-            if r is not None and len(r) != len(c):
-                raise ValueError("len(rev) != len(col)")
-            L.call("fu_lossy_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), L.ptr(self.values),
-                   int(device), ctypes.byref(out))
-            self.n, self.E = n, int(rp[-1])
-        self._h = out
+        self._open(graph, values, rowptr, col, rev, device)
         if loss != 0.0 or seed != 0:
             self.set_loss(loss, seed)
 
@@ -357,80 +337,12 @@ class CollectAllLossy:
 
     def set_values(self, values):
         """New inputs; flows, estimates and the round counter are kept."""
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        if v.shape != (self.n,):
-            raise ValueError(f"values must have shape ({self.n},), got {v.shape}")
-        L.call("fu_lossy_set_values", self._h, L.ptr(v))
-        self.values = v
-
-    def reset(self):
-        L.call("fu_lossy_reset", self._h)
-
-    def set_targets(self, target):
-        t = np.ascontiguousarray(target, dtype=np.float64)
-        if t.shape != (self.n,):
-            raise ValueError(f"targets must have shape ({self.n},), got {t.shape}")
-        L.call("fu_lossy_set_targets", self._h, L.ptr(t))
-
-    def run(self, rounds: int, err_every: int = 0):
-        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
-        if err_every > 0:
-            trace = np.empty(max(rounds // err_every, 1))
-            L.call("fu_lossy_run", self._h, int(rounds), int(err_every), L.ptr(trace))
-            return trace[:rounds // err_every]
-        L.call("fu_lossy_run", self._h, int(rounds), 0, None)
-        return None
-
-    def run_timed(self, rounds: int) -> float:
-        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
-        ms = L.f32()
-        L.call("fu_lossy_run_timed", self._h, int(rounds), ctypes.byref(ms))
-        return float(ms.value)
-
-    def max_err(self) -> float:
-        out = L.f64()
-        L.call("fu_lossy_max_err", self._h, ctypes.byref(out))
-        return float(out.value)
-
-    def estimates(self) -> np.ndarray:
-        a = np.empty(self.n)
-        L.call("fu_lossy_get_estimates", self._h, L.ptr(a))
-        return a
-
-    def flows(self) -> np.ndarray:
-        f = np.empty(max(self.E, 1))
-        L.call("fu_lossy_get_flows", self._h, L.ptr(f))
-        return f[:self.E]
-
-    @property
-    def rounds_done(self) -> int:
-        r = L.i64()
-        L.call("fu_lossy_get_round", self._h, ctypes.byref(r))
-        return int(r.value)
+        self._set_values(values)
 
     @property
     def stats(self) -> tuple:
         """(messages offered, messages lost) since the last reset; synchronises."""
-        s = np.zeros(2, dtype=np.int64)
-        L.call("fu_lossy_get_stats", self._h, L.ptr(s))
-        return int(s[0]), int(s[1])
-
-    def synchronize(self):
-        L.call("fu_lossy_synchronize", self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib.fu_lossy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._stats()
 
 
 def pair_matching(g, seed: int, r: int):
@@ -447,7 +359,7 @@ def pair_matching(g, seed: int, r: int):
     return mate[:n], init[:n]
 
 
-class PairwiseSync:
+class PairwiseSync(_Handle):
     """Synchronous pairwise rounds (fu_pair_*): every round a matching of the graph is chosen on
     the device (a pure function of seed, round and graph) and each matched pair runs one full
     pairwise exchange: the initiator fires (PW:102-117), the listener receives and fires back,
@@ -458,31 +370,11 @@ class PairwiseSync:
     >>> eng.run(1000); est = eng.estimates(); pairs, never_fired = eng.stats
     """
 
+    _C = _c_names("fu_pair_")
+
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
                  seed: int = 0, device: int = 0):
-        v = np.asarray(values, dtype=np.float64)
-        if v.ndim != 1:
-            raise ValueError(f"values must have shape (n,), got {v.shape}")
-        self.values = np.ascontiguousarray(v)
-        out = L.vp()
-        if graph is not None:
-            if len(v) != graph.n:
-                raise ValueError("len(values) != graph.n")
-            L.call("fu_pair_create_from_graph", graph._h, L.ptr(self.values), int(device), ctypes.byref(out))
-            self.n, self.E = graph.n, graph.E
-        else:
-            rp = np.ascontiguousarray(rowptr, dtype=np.int64)
-            c = np.ascontiguousarray(col, dtype=np.int32)
-            r = None if rev is None else np.ascontiguousarray(rev, dtype=np.int32)
-            n = len(rp) - 1
-            if len(v) != n:
-                raise ValueError("len(values) != n")
-            if r is not None and len(r) != len(c):
-                raise ValueError("len(rev) != len(col)")
-            L.call("fu_pair_create", n, int(rp[-1]), L.ptr(rp), L.ptr(c), L.ptr(r), L.ptr(self.values),
-                   int(device), ctypes.byref(out))
-            self.n, self.E = n, int(rp[-1])
-        self._h = out
+        self._open(graph, values, rowptr, col, rev, device)
         if seed != 0:
             self.set_seed(seed)
 
@@ -496,51 +388,11 @@ class PairwiseSync:
 
     def set_values(self, values):
         """New inputs; flows, caches, last averages and the round counter are kept."""
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        if v.shape != (self.n,):
-            raise ValueError(f"values must have shape ({self.n},), got {v.shape}")
-        L.call("fu_pair_set_values", self._h, L.ptr(v))
-        self.values = v
-
-    def reset(self):
-        L.call("fu_pair_reset", self._h)
-
-    def set_targets(self, target):
-        t = np.ascontiguousarray(target, dtype=np.float64)
-        if t.shape != (self.n,):
-            raise ValueError(f"targets must have shape ({self.n},), got {t.shape}")
-        L.call("fu_pair_set_targets", self._h, L.ptr(t))
-
-    def run(self, rounds: int, err_every: int = 0):
-        """Run `rounds` rounds; with err_every > 0 returns the max-error trace."""
-        if err_every > 0:
-            trace = np.empty(max(rounds // err_every, 1))
-            L.call("fu_pair_run", self._h, int(rounds), int(err_every), L.ptr(trace))
-            return trace[:rounds // err_every]
-        L.call("fu_pair_run", self._h, int(rounds), 0, None)
-        return None
-
-    def run_timed(self, rounds: int) -> float:
-        """Device milliseconds for `rounds` rounds (HIP events on the handle's stream)."""
-        ms = L.f32()
-        L.call("fu_pair_run_timed", self._h, int(rounds), ctypes.byref(ms))
-        return float(ms.value)
-
-    def max_err(self) -> float:
-        out = L.f64()
-        L.call("fu_pair_max_err", self._h, ctypes.byref(out))
-        return float(out.value)
+        self._set_values(values)
 
     def estimates(self) -> np.ndarray:
         """Every node's average at its last fire (0.0 before its first)."""
-        a = np.empty(self.n)
-        L.call("fu_pair_get_estimates", self._h, L.ptr(a))
-        return a
-
-    def flows(self) -> np.ndarray:
-        f = np.empty(max(self.E, 1))
-        L.call("fu_pair_get_flows", self._h, L.ptr(f))
-        return f[:self.E]
+        return super().estimates()
 
     def cache(self) -> np.ndarray:
         """The cached estimate of every slot."""
@@ -549,34 +401,9 @@ class PairwiseSync:
         return c[:self.E]
 
     @property
-    def rounds_done(self) -> int:
-        r = L.i64()
-        L.call("fu_pair_get_round", self._h, ctypes.byref(r))
-        return int(r.value)
-
-    @property
     def stats(self) -> tuple:
         """(pairs exchanged, nodes that have never fired) since the last reset; synchronises."""
-        s = np.zeros(2, dtype=np.int64)
-        L.call("fu_pair_get_stats", self._h, L.ptr(s))
-        return int(s[0]), int(s[1])
-
-    def synchronize(self):
-        L.call("fu_pair_synchronize", self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib.fu_pair_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._stats()
 
 
 class Trace:
