@@ -300,6 +300,72 @@ int fu_lossy_delivered(uint64_t seed, int64_t round, int64_t first, int64_t coun
                        uint8_t *out);
 
 /* ======================================================================================
+ * Churn collect-all engine: the synchronous round over a fixed CSR whose nodes and links are
+ * switched off and on between runs (nodes that crash or arrive, links that disappear or
+ * return). A node that may ever join is in the graph from the start, switched off.
+ *
+ * State: per directed slot k = (i -> j), in the caller's CSR order, the flow f[k] and a slot
+ * state UP, DOWN or FRESH; per node the estimate a[i], the input v[i] and alive[i].
+ * Topology: the pair (alive[n], link_up[e]), given whole at every call, NULL = all ones;
+ * link_up[k] != link_up[rev k] is FU_ERR_ARG. Slot k is live iff link_up[k] && alive[i] &&
+ * alive[col k]. Applying a topology moves a slot
+ *   live -> not live: DOWN. Both ends drop the neighbour; its flow entry is gone (f[k] = +0.0).
+ *   not live -> live: FRESH. The neighbour was just added; nothing has been received from it.
+ *   live -> live:     as it was (UP stays UP; FRESH stays FRESH if no round ran in between).
+ * After create and after reset every live slot is FRESH and all state is zero, so round 0 is
+ * the timeout fire on zero state without a special case.
+ * Round r, alive node i: row i's slots in row order, the DOWN ones skipped;
+ *   UP slot:    F = -f_old[rev k],  E = a_old[col k]          (CA:98-99)
+ *   FRESH slot: F = 0.0,            E = 0.0                   (CA:33-34)
+ *   S = 0.0 + F..,  T = 0.0 + E.. left to right,  d = the number of live slots,
+ *   a_new[i] = ((v[i] - S) + T) / (double)(d + 1),
+ *   f_new[k] = (F + a_new[i]) - E for the live slots, +0.0 for the DOWN ones;
+ * after the round every FRESH slot is UP. A dead node does not fire (a_new[i] = a_old[i]) and
+ * all its slots are DOWN; an alive node whose slots are all DOWN gets a = v.
+ * With everything alive and up the rounds are bit-equal to fu_run_collectall; a topology set
+ * before round 0 and never changed gives fu_run_collectall on the live subgraph (live slots
+ * only, row order kept); run(17) equals run(5); run(12); after any sequence of events the
+ * alive nodes converge to the mean of the alive inputs of their component of the live graph.
+ * The reverse flow is gathered through rev, as in the lossy engine. Arguments are checked
+ * before any HIP call, also on a host without a GPU.
+ * ==================================================================================== */
+typedef struct fu_churn fu_churn;
+
+/* As fu_lossy_create (rev may be NULL: built natively; a caller's rev is validated). Everything
+ * starts alive and up. */
+int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                    const int32_t *rev, const double *value, int32_t device, fu_churn **out);
+int fu_churn_create_from_graph(const fu_graph *g, const double *value, int32_t device,
+                               fu_churn **out);
+/* alive[n] and link_up[e], non-zero = on, NULL = all ones. Ordered behind the rounds already
+ * queued; complete on return. */
+int fu_churn_set_topology(fu_churn *h, const uint8_t *alive, const uint8_t *link_up);
+/* The inputs change (value[n]); flows, estimates, states and the round counter are kept. */
+int fu_churn_set_values(fu_churn *h, const double *value);
+/* Zero the state and the round counter; topology and values are kept; live slots FRESH. */
+int fu_churn_reset(fu_churn *h);
+/* As fu_lossy_run, but the error entries are the maximum of |a_i - target_i| over the alive
+ * nodes only (+0.0 if none is alive). */
+int fu_churn_run(fu_churn *h, int32_t rounds, int32_t err_every, double *err_trace);
+int fu_churn_run_timed(fu_churn *h, int32_t rounds, float *ms);
+int fu_churn_set_targets(fu_churn *h, const double *target);
+int fu_churn_max_err(fu_churn *h, double *out);
+int fu_churn_get_estimates(fu_churn *h, double *a_out /* n */);
+int fu_churn_get_flows(fu_churn *h, double *f_out /* e */);
+int fu_churn_get_round(fu_churn *h, int64_t *rounds_done);
+/* out[0] = alive nodes, out[1] = live directed slots, of the current topology. */
+int fu_churn_get_stats(fu_churn *h, int64_t out[2]);
+/* state_out[e]: 0 UP, 1 DOWN, 2 FRESH. */
+int fu_churn_get_slot_state(fu_churn *h, uint8_t *state_out);
+int fu_churn_synchronize(fu_churn *h);
+int fu_churn_destroy(fu_churn *h);
+/* Host only, no GPU: live_out[k] (e = rowptr[n] bytes) of a topology; alive, link_up and rev
+ * may be NULL. FU_ERR_ARG if link_up is not symmetric under rev or the CSR is malformed,
+ * FU_ERR_GRAPH for an asymmetric graph or a bad rev. */
+int fu_churn_live(int32_t n, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                  const uint8_t *alive, const uint8_t *link_up, uint8_t *live_out);
+
+/* ======================================================================================
  * Synchronous pairwise engine: every round a matching of the graph is chosen on the device
  * and each matched pair runs one full pairwise exchange. State: per directed slot k (the
  * caller's CSR order) the flow f[k] and the cached estimate c[k], per node last[i] (last_avg,

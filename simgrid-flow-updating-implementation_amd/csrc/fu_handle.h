@@ -1,5 +1,6 @@
-// The handle scaffold of the batched, lossy and pairwise engines: included by fu_batch.hip,
-// fu_lossy.hip and fu_pair.hip and by nothing else. DESIGN.md §4.15-4.17.
+// The handle scaffold of the batched, lossy, pairwise and churn engines: included by
+// fu_batch.hip, fu_lossy.hip, fu_pair.hip and fu_churn.hip and by nothing else. DESIGN.md
+// §4.15-4.18.
 //
 // An engine's handle derives from fu::handle_base, names itself in `kTag` ("fu_batch", ...:
 // the prefix of its entry points and of every message), and supplies

@@ -6,6 +6,7 @@
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 [--churn-seed 7]
 
 Defaults mirror flowupdating-collectall.py:154,157 (./platforms/small_platform.xml,
 ./actors.xml, watcher 1000.0 / 10.0 at CA:162).
@@ -16,7 +17,7 @@ import argparse
 import sys
 import time
 
-from .engine import CollectAll, CollectAllLossy, PairwiseSync
+from .engine import CollectAll, CollectAllChurn, CollectAllLossy, PairwiseSync, churn_targets
 from .graph import Graph, component_means, uniform_values
 from .sim import CollectAllPeer, Engine, run_reference_main
 
@@ -39,7 +40,28 @@ def main(argv=None):
     ap.add_argument("--loss-seed", type=int, default=0)
     ap.add_argument("--pairs", action="store_true", help="bench-graph: synchronous pairwise rounds (pair engine)")
     ap.add_argument("--pair-seed", type=int, default=0)
+    ap.add_argument("--churn", type=float, default=None,
+                    help="bench-graph: fraction of the nodes that dies after half of the rounds (churn engine)")
+    ap.add_argument("--churn-seed", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.mode == "bench-graph" and a.churn is not None:
+        if a.loss is not None or a.pairs:
+            ap.error("--churn is exclusive with --loss and --pairs")
+        g = Graph.from_spec(a.spec, seed=a.seed)
+        v = uniform_values(g.n, seed=0)
+        eng = CollectAllChurn(g, v, device=a.device)
+        # node i dies iff U_i < FRACTION, U the fu_values_uniform stream at the churn seed
+        alive = ~(uniform_values(g.n, seed=a.churn_seed, lo=0.0, hi=1.0) < a.churn)
+        t0 = time.perf_counter()
+        ms = eng.run_timed(a.rounds // 2)
+        eng.set_topology(alive=alive)
+        eng.set_targets(churn_targets(g, v, alive))
+        ms += eng.run_timed(a.rounds - a.rounds // 2)
+        wall = time.perf_counter() - t0
+        print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
+              f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
+              f"max_err={eng.max_err():.3e} alive={eng.stats[0]}")
+        return 0
     if a.mode == "bench-graph" and a.pairs:
         if a.loss is not None:
             ap.error("--pairs and --loss are exclusive")

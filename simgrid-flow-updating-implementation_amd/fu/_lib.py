@@ -107,6 +107,23 @@ _SIGS = {
     "fu_lossy_synchronize": ([vp], ctypes.c_int),
     "fu_lossy_destroy": ([vp], ctypes.c_int),
     "fu_lossy_delivered": ([u64, i64, i64, i64, f64, vp], ctypes.c_int),
+    "fu_churn_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_churn_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_churn_set_topology": ([vp, vp, vp], ctypes.c_int),
+    "fu_churn_set_values": ([vp, vp], ctypes.c_int),
+    "fu_churn_reset": ([vp], ctypes.c_int),
+    "fu_churn_run": ([vp, i32, i32, vp], ctypes.c_int),
+    "fu_churn_run_timed": ([vp, i32, P(f32)], ctypes.c_int),
+    "fu_churn_set_targets": ([vp, vp], ctypes.c_int),
+    "fu_churn_max_err": ([vp, P(f64)], ctypes.c_int),
+    "fu_churn_get_estimates": ([vp, vp], ctypes.c_int),
+    "fu_churn_get_flows": ([vp, vp], ctypes.c_int),
+    "fu_churn_get_round": ([vp, P(i64)], ctypes.c_int),
+    "fu_churn_get_stats": ([vp, vp], ctypes.c_int),
+    "fu_churn_get_slot_state": ([vp, vp], ctypes.c_int),
+    "fu_churn_synchronize": ([vp], ctypes.c_int),
+    "fu_churn_destroy": ([vp], ctypes.c_int),
+    "fu_churn_live": ([i32, vp, vp, vp, vp, vp, vp], ctypes.c_int),
     "fu_pair_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
     "fu_pair_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
     "fu_pair_set_seed": ([vp, u64], ctypes.c_int),

@@ -8,6 +8,9 @@
   K-wide estimate gather per edge; each column is bit-equal to a `CollectAll` run.
 * `CollectAllLossy`: the same rounds with a loss model (fu_lossy_*): a lost message makes the
   receiver fire on its own stored flow and estimate; the reverse flow is gathered through rev.
+* `CollectAllChurn`: the same rounds while nodes and links leave and join (fu_churn_*): a slot
+  state per directed slot (UP, DOWN, FRESH); a removed neighbour drops out of both sums and of
+  the divisor, an added one starts from zeros; `churn_live` / `churn_targets` on the host.
 * `PairwiseSync`: synchronous pairwise rounds (fu_pair_*): a matching per round chosen on the
   device, one full pairwise exchange per matched pair; `pair_matching` restates it on the host.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
@@ -21,7 +24,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from .graph import Graph
+from .graph import Graph, component_means
 
 KERNELS = {"auto": 0, "recon": 4, "stage": 8, "pregather": 9}
 LAYOUTS = {"given": 0, "degree": 1}
@@ -343,6 +346,92 @@ class CollectAllLossy(_Handle):
     def stats(self) -> tuple:
         """(messages offered, messages lost) since the last reset; synchronises."""
         return self._stats()
+
+
+def _csr_of(g):
+    """(rowptr, col, rev) of a Graph or of a (rowptr, col, rev) triple, rev None allowed."""
+    rowptr, col, rev = g.arrays() if isinstance(g, Graph) else g
+    return (np.ascontiguousarray(rowptr, dtype=np.int64), np.ascontiguousarray(col, dtype=np.int32),
+            None if rev is None else np.ascontiguousarray(rev, dtype=np.int32))
+
+
+def _mask(x, size: int, name: str):
+    """A topology mask as uint8[size], or None; ValueError for another shape or a non-integer,
+    non-boolean dtype."""
+    if x is None:
+        return None
+    m = np.asarray(x)
+    if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+        raise ValueError(f"{name} must be boolean or integer, got {m.dtype}")
+    if m.shape != (size,):
+        raise ValueError(f"{name} must have shape ({size},), got {m.shape}")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+def churn_live(g, alive=None, link_up=None) -> np.ndarray:
+    """uint8[E]: 1 where slot k = (i -> j) is live under (alive, link_up): link_up[k] and alive[i]
+    and alive[j]; None = all ones. g: a Graph or (rowptr, col, rev). The liveness rule of
+    `CollectAllChurn` on the host (fu_churn_live; no GPU); FuError if link_up differs between a
+    slot and its reverse."""
+    rp, col, rev = _csr_of(g)
+    n, E = len(rp) - 1, int(rp[-1])
+    a, u = _mask(alive, n, "alive"), _mask(link_up, E, "link_up")
+    out = np.empty(max(E, 1), dtype=np.uint8)
+    z = lambda x: L.ptr(x) if x is not None and len(x) else None  # noqa: E731
+    L.call("fu_churn_live", n, L.ptr(rp), z(col), z(rev), L.ptr(a), z(u), L.ptr(out))
+    return out[:E]
+
+
+def churn_targets(g, values, alive=None, link_up=None) -> np.ndarray:
+    """What `CollectAllChurn` converges to under (alive, link_up): per alive node the exact mean
+    of the alive inputs of its component of the live graph (`component_means` of the live
+    subgraph, in the caller's numbering). A dead node's entry is its own value."""
+    rp, col, _ = _csr_of(g)
+    live = churn_live(g, alive, link_up).astype(bool)
+    src = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    lrp = np.concatenate([[0], np.cumsum(np.bincount(src[live], minlength=len(rp) - 1))]).astype(np.int64)
+    return component_means(lrp, col[live], values)[0]
+
+
+class CollectAllChurn(_Handle):
+    """Synchronous collect-all rounds while nodes and links leave and join (fu_churn_*): between
+    runs, `set_topology` switches nodes and links of the fixed graph off and on. A removed
+    neighbour drops out of both sums and of the divisor and its flow entry is gone; an added one
+    starts from zeros (CA:33-34, CA:94-96); a dead node keeps its last estimate. The alive nodes
+    converge to the mean of the alive inputs of their component. With everything alive this is
+    `CollectAll`, bit for bit.
+
+    >>> eng = CollectAllChurn(g, v); eng.run(100)
+    >>> alive = np.ones(g.n, np.uint8); alive[:1000] = 0
+    >>> eng.set_topology(alive=alive); eng.set_targets(churn_targets(g, v, alive)); eng.run(400)
+    """
+
+    _C = _c_names("fu_churn_", set_topology="fu_churn_set_topology", get_slot_state="fu_churn_get_slot_state")
+    UP, DOWN, FRESH = 0, 1, 2
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None, device: int = 0):
+        self._open(graph, values, rowptr, col, rev, device)
+
+    def set_topology(self, alive=None, link_up=None):
+        """alive: n entries, link_up: E entries (the same on a slot and its reverse), non-zero =
+        on, None = all on. The whole topology of the rounds run from now on."""
+        a, u = _mask(alive, self.n, "alive"), _mask(link_up, self.E, "link_up")
+        self._call("set_topology", L.ptr(a), L.ptr(u) if self.E else None)
+
+    def set_values(self, values):
+        """New inputs; flows, estimates, slot states and the round counter are kept."""
+        self._set_values(values)
+
+    @property
+    def stats(self) -> tuple:
+        """(alive nodes, live directed slots) of the current topology."""
+        return self._stats()
+
+    def slot_state(self) -> np.ndarray:
+        """uint8[E]: UP (0), DOWN (1) or FRESH (2) per slot."""
+        s = np.empty(max(self.E, 1), dtype=np.uint8)
+        self._call("get_slot_state", L.ptr(s))
+        return s[:self.E]
 
 
 def pair_matching(g, seed: int, r: int):
