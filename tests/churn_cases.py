@@ -21,6 +21,9 @@ from lossy_cases import TILE_HEAVY_DEG, TILE_ROWS, TILE_SLOTS, hub60, tile_censu
 
 UP, DOWN, FRESH = 0, 1, 2
 HEAVY_CHUNK = 2048  # slots of a heavy row (degree > TILE_HEAVY_DEG) staged per chunk (fu_churn.hip kChunk)
+# chunk_edge_graph()'s heavy rows: the first heavy degree, one slot short of a chunk, a chunk, a chunk and one
+# slot, two chunks, two chunks and one slot
+CHUNK_EDGE_DEGREES = (TILE_HEAVY_DEG + 1, HEAVY_CHUNK - 1, HEAVY_CHUNK, HEAVY_CHUNK + 1, 2 * HEAVY_CHUNK, 2 * HEAVY_CHUNK + 1)
 
 Step = collections.namedtuple("Step", "a f state alive_nodes live_slots")
 Result = collections.namedtuple("Result", "a f state a_rounds f_rounds steps")
@@ -188,3 +191,179 @@ def scripted_run(g, seed, values2):
     assert len(dead) >= 2 and len(down) >= 2
     return [("run", 6), ("topology", alive1, up1), ("run", 1), ("topology", alive2, up2), ("run", 1), ("values", values2),
             ("run", 5), ("topology", alive3, up3), ("topology", alive2, up2), ("run", 4), ("reset",), ("run", 3)]
+
+
+# ------------------------------------------------------------------------------------
+# heavy rows at the chunk edges
+# ------------------------------------------------------------------------------------
+CHUNK_EDGE_ORDER = (2049, 4096, 4097, 2048, 2047, 129)  # by id: the first three rows, the middle one, the last two
+CHUNK_EDGE_CHAIN = 4  # every 4th leaf is linked to the next leaf
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_edge_graph():
+    """Six heavy rows of the degrees CHUNK_EDGE_DEGREES, pairwise linked, the rest of each row's
+    degree leaves of its own (14636 leaves, taken in id order row after row), and every 4th leaf
+    linked to the next one so that the light tiles hold slots whose two ends are both light. Ids:
+    heavy rows at 0, 1, 2 (the first tile starts after three adjacent heavy rows), one between
+    the two halves of the leaves (it closes a tile), two at n-2 and n-1 (no tile after the last
+    row). A row's slots are in ascending neighbour id, so a heavy row's heavy-heavy slots are
+    its first ones, the one to the middle row, and its last ones."""
+    assert sorted(CHUNK_EDGE_ORDER) == list(CHUNK_EDGE_DEGREES)
+    k = len(CHUNK_EDGE_ORDER)
+    n_leaf = sum(CHUNK_EDGE_ORDER) - k * (k - 1)
+    n = k + n_leaf
+    heavy = [0, 1, 2, 3 + n_leaf // 2, n - 2, n - 1]
+    leaves = np.setdiff1d(np.arange(n), heavy)
+    src = [np.array([heavy[p] for p in range(k) for q in range(p + 1, k)])]
+    dst = [np.array([heavy[q] for p in range(k) for q in range(p + 1, k)])]
+    first = 0
+    for h, d in zip(heavy, CHUNK_EDGE_ORDER):
+        src.append(np.full(d - (k - 1), h))
+        dst.append(leaves[first:first + d - (k - 1)])
+        first += d - (k - 1)
+    assert first == n_leaf
+    src.append(leaves[:-1:CHUNK_EDGE_CHAIN])
+    dst.append(leaves[1::CHUNK_EDGE_CHAIN])
+    g = fu.Graph.from_edges(n, np.concatenate(src), np.concatenate(dst))
+    assert [int(g.degrees[h]) for h in heavy] == list(CHUNK_EDGE_ORDER) and heavy_rows(g) == heavy
+    return g
+
+
+def chunk_edge_rows():
+    """{degree: id} of chunk_edge_graph()'s heavy rows."""
+    g = chunk_edge_graph()
+    return {int(g.degrees[h]): h for h in heavy_rows(g)}
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_edge_topology(which):
+    """(alive, link_up) on chunk_edge_graph(): about a tenth of the leaves dead and a twentieth of
+    the links down (the heavy rows kept alive), and on top, slots picked by their position in
+    the row:
+      "A": on the rows above one chunk (2049, 4096, 4097) slots 0, 2047, 2048 and d-1 DOWN; the
+           2048 row alive with every link cut; the 2047 row dead, all its neighbours alive;
+      "B": slot 2048 the only live slot of the 2049 row; the second chunk of the 4096 row (slots
+           2048 .. 4095) DOWN;
+      "C": slot 2048 the only DOWN slot of the 2049 row; the middle chunk of the 4097 row DOWN.
+    tests/test_churn_case_inputs.py asserts each of these on the masks."""
+    g = chunk_edge_graph()
+    row = chunk_edge_rows()
+    alive, up = random_masks(g, 0.1, 0.05, 30 + "ABC".index(which), keep=heavy_rows(g))
+    c = HEAVY_CHUNK
+    if which == "A":
+        for d in (2049, 4096, 4097):
+            up = cut(g, up, row_slots(g, row[d])[[0, c - 1, c, d - 1]])
+        up = cut(g, up, row_slots(g, row[2048]))
+        alive[g.col[row_slots(g, row[2047])]] = 1
+        alive[row[2047]] = 0
+    elif which == "B":
+        hs = row_slots(g, row[2049])
+        up = cut(g, up, np.delete(hs, c))
+        alive[g.col[hs[c]]] = 1
+        up[[hs[c], g.rev[hs[c]]]] = 1
+        up = cut(g, up, row_slots(g, row[4096])[c:2 * c])
+    else:
+        up = cut(g, up, row_slots(g, row[4097])[c:2 * c])
+        hs = row_slots(g, row[2049])
+        alive[g.col[hs]] = 1
+        up[hs] = 1
+        up[g.rev[hs]] = 1
+        up = cut(g, up, hs[[c]])
+    alive.setflags(write=False)
+    up.setflags(write=False)
+    return alive, up
+
+
+def chunk_edge_values(family):
+    """The inputs of the chunk-edge cases. "special" plants -0.0, +inf and -inf on three leaves of
+    the 4097 row that stay alive and linked throughout the script (the row's T chain reaches
+    inf - inf in round 1) and a NaN on such a leaf of the 4096 row; "subn" is parity_util's."""
+    from parity_util import FAMILIES
+
+    g = chunk_edge_graph()
+    if family == "uniform":
+        return fu.uniform_values(g.n, seed=3)
+    if family == "subn":
+        return FAMILIES["subn"](g.n, 4)
+    assert family == "special"
+    v = fu.uniform_values(g.n, seed=3)
+    alive, up = chunk_edge_topology("A")
+    live = live_np(*g.arrays(), alive, up)
+    row = chunk_edge_rows()
+    hs = row_slots(g, row[4097])
+    ok = hs[live[hs] & (g.degrees[g.col[hs]] <= 2)]
+    v[g.col[ok[[10, len(ok) // 2, len(ok) - 10]]]] = [-0.0, np.inf, -np.inf]
+    hs = row_slots(g, row[4096])
+    v[g.col[hs[live[hs] & (g.degrees[g.col[hs]] <= 2)][20]]] = np.nan
+    return v
+
+
+def revival(g, alive, up):
+    """(alive, link_up) with every other dead node alive again and every other cut link restored."""
+    dead = np.flatnonzero(np.asarray(alive) == 0)
+    down = np.flatnonzero((np.asarray(up) == 0) & (np.arange(g.E) < g.rev))
+    assert len(dead) >= 2 and len(down) >= 2
+    alive2 = np.array(alive, dtype=np.uint8)
+    alive2[dead[::2]] = 1
+    return alive2, cut(g, np.ones(g.E, dtype=np.uint8), down[1::2])
+
+
+CHUNK_EDGE_REVIVAL = 4  # the index of the revival in chunk_edge_script()
+
+
+def chunk_edge_script():
+    """run(3); topology "A"; run(1); run(2); revive half of the dead and restore half of the cut
+    links, the last slot of every row above one chunk among them; run(1); run(2); reset; run(2)."""
+    g = chunk_edge_graph()
+    alive, up = chunk_edge_topology("A")
+    alive2, up2 = revival(g, alive, up)
+    for d, h in chunk_edge_rows().items():
+        if d > HEAVY_CHUNK:
+            k = row_slots(g, h)[-1]
+            alive2[g.col[k]] = 1
+            up2[[k, g.rev[k]]] = 1
+    return [("run", 3), ("topology", alive, up), ("run", 1), ("run", 2), ("topology", alive2, up2), ("run", 1), ("run", 2),
+            ("reset",), ("run", 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_edge_case(family):
+    """(g, v, script, the restatement's Result) of the scripted chunk-edge run."""
+    g, v, script = chunk_edge_graph(), chunk_edge_values(family), chunk_edge_script()
+    return g, v, script, churn_python(*g.arrays(), v, script)
+
+
+# ------------------------------------------------------------------------------------
+# a topology call before every round
+# ------------------------------------------------------------------------------------
+FLAP_ROUNDS = 10
+
+
+@functools.lru_cache(maxsize=None)
+def flapping_case():
+    """(g, v, script, Result) on tile_limit_graph(): FLAP_ROUNDS times a topology of fresh random
+    masks (the heavy row kept alive) and one round."""
+    g = tile_limit_graph()
+    v = fu.uniform_values(g.n, seed=3)
+    h = tile_segment("heavy")[0]
+    script = []
+    for r in range(FLAP_ROUNDS):
+        script += [("topology",) + random_masks(g, 0.15, 0.15, 50 + r, keep=(h,)), ("run", 1)]
+    return g, v, script, churn_python(*g.arrays(), v, script)
+
+
+# ------------------------------------------------------------------------------------
+# mask bytes other than 0 and 1
+# ------------------------------------------------------------------------------------
+def byte_masks(g, seed):
+    """(alive, link_up) as a C caller may pass them (include/fu.h: non-zero = on): alive bytes from
+    {0, 1, 2, 128, 255}; link_up bytes from {0, 7, 255}, zero on both slots of a link or on
+    neither, and where on, 7 on one slot and 255 on its reverse."""
+    rng = np.random.default_rng(seed)
+    alive = rng.choice(np.array([0, 1, 2, 128, 255], dtype=np.uint8), size=g.n)
+    on = random_masks(g, 0.0, 0.25, seed)[1] != 0
+    up = np.where(on, np.where(np.arange(g.E) < g.rev, 7, 255), 0).astype(np.uint8)
+    assert set(alive.tolist()) == {0, 1, 2, 128, 255} and set(up.tolist()) == {0, 7, 255}
+    assert np.array_equal(up != 0, up[g.rev] != 0) and (up[on] != up[g.rev][on]).all()
+    return alive, up

@@ -205,6 +205,36 @@ def err_scalar_reducer_case():
     return g, v, oracle_rounds(g.arrays(), v, ERR_REDUCER_R), probes, np.asarray(new_of_old, dtype=np.int64)
 
 
+ERR_CHURN_DECOY = 2.0 ** 20  # a dead decoy's target sits this many D off its estimate
+
+
+@functools.lru_cache(maxsize=None)
+def err_churn_reducer_case():
+    """Section 5, kc_max_err (fu_churn.hip): (g, v, alive, a_rounds, probes, decoys). The graph,
+    values and probes of err_scalar_reducer_case under a static topology with about a tenth of
+    the nodes dead (the probes kept alive), set before round 0: a_rounds is the C oracle on the
+    live subgraph, and a dead node stays at 0.0. decoys: a dead node of block 0, one of the last
+    block of the first stride and one of the second stride."""
+    from churn_cases import compact, live_np, random_masks
+
+    g, v, _, probes, _ = err_scalar_reducer_case()
+    alive, _ = random_masks(g, 0.1, 0.0, 5, keep=probes)
+    rp, col, rev, _ = compact(*g.arrays(), live_np(*g.arrays(), alive, None))
+    a_rounds = oracle_rounds((rp, col, rev), v, ERR_REDUCER_R)
+    a_rounds[:, alive == 0] = 0.0
+    dead = np.flatnonzero(alive == 0)
+    stride = ERR_GRID * 256
+    decoys = [int(dead[0]), int(dead[dead >= stride - 256][0]), int(dead[dead >= stride][0])]
+    return g, v, alive, a_rounds, probes, decoys
+
+
+def with_decoys(t, a_last, decoys, D):
+    """t with every decoy's target ERR_CHURN_DECOY * D above its estimate."""
+    t = t.copy()
+    t[decoys] = a_last[decoys] + ERR_CHURN_DECOY * D
+    return t
+
+
 ERR_BATCH_KS = (16, 7, 3)
 
 
@@ -266,6 +296,9 @@ def planted_conditions(case):
         g, _, a, probes, new_of_old = err_scalar_reducer_case()
         old_of_new = np.argsort(new_of_old)
         return [(a, p, planted_D(a)) for p in _unique(probes + [old_of_new[q] for q in probes])]
+    if case == "churn_reducer":
+        _, _, _, a, probes, _ = err_churn_reducer_case()
+        return [(a, p, planted_D(a)) for p in probes]
     if case.startswith("batch:"):
         K = int(case.split(":")[1])
         g, _, a, probes, D = err_batch_case(K)
@@ -276,5 +309,5 @@ def planted_conditions(case):
     raise KeyError(case)
 
 
-PLANTED_CASES = (["classes", "rmat", "rccl", "scalar_reducer"] + [f"isolated:{t}" for t in ISO_TAILS]
+PLANTED_CASES = (["classes", "rmat", "rccl", "scalar_reducer", "churn_reducer"] + [f"isolated:{t}" for t in ISO_TAILS]
                  + [f"dist:{k}:{w}" for k, w in ERR_DIST_CASES] + [f"batch:{K}" for K in ERR_BATCH_KS])

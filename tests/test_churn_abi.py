@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import fu
-from churn_cases import cut, hub60, live_np, random_masks
+from churn_cases import byte_masks, cut, hub60, live_np, random_masks
 from fu import _lib as L
 
 CHURN_SYMBOLS = ["fu_churn_create", "fu_churn_create_from_graph", "fu_churn_set_topology", "fu_churn_set_values",
@@ -55,6 +55,22 @@ def test_live_equals_the_numpy_rule():
     alive, up = random_masks(g, 0.2, 0.2, 9)
     assert np.array_equal(_live(rp, col, rev, alive, None)[1].astype(bool), live_np(rp, col, rev, alive, None))
     assert np.array_equal(_live(rp, col, rev, None, up)[1].astype(bool), up.astype(bool))
+
+
+def test_live_with_mask_bytes_other_than_0_and_1():
+    """The masks of test_churn_gpu.test_any_nonzero_mask_byte_is_on: alive bytes from {0, 1, 2,
+    128, 255}, link_up 7 on a slot and 255 on its reverse. The symmetry check compares zero with
+    non-zero, not the bytes, and the answer is the one for the same masks as 0 / 1."""
+    g = hub60()
+    rp, col, rev = g.arrays()
+    alive, up = byte_masks(g, 71)
+    want = live_np(rp, col, rev, alive != 0, up != 0)
+    assert 0 < want.sum() < (up != 0).sum()
+    for r in (rev, None):
+        rc, got = _live(rp, col, r, alive, up)
+        assert rc == 0 and np.array_equal(got, want.astype(np.uint8))  # 0 / 1 out, whatever came in
+        rc, norm = _live(rp, col, r, (alive != 0).astype(np.uint8), (up != 0).astype(np.uint8))
+        assert rc == 0 and np.array_equal(got, norm)
 
 
 def test_live_with_a_dead_hub():

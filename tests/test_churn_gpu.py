@@ -6,7 +6,12 @@ and exact on the slot states and the counts.
 
 The kernel's row classes change at degree 128 (light tiles of at most 256 rows and 2048 slots /
 one block per row, staged in chunks of 2048 slots): lossy_cases.tile_limit_graph() closes its
-tiles in every way and has one row of degree 129, star(2100)'s hub row spans two chunks."""
+tiles in every way and has one row of degree 129, star(2100)'s hub row spans two chunks, and
+churn_cases.chunk_edge_graph() has six heavy rows of one slot under a chunk, a chunk, a chunk and
+one slot, two chunks, two chunks and one slot, linked to each other, at the first, a middle and the
+last ids. Sections 8-11 run on it, on a topology call before every round, on graphs of one node,
+no link, one link and more nodes than slots, and on mask bytes other than 0 and 1; the conditions
+on their inputs are tests/test_churn_case_inputs.py's, on any host."""
 import functools
 
 import numpy as np
@@ -14,9 +19,11 @@ import pytest
 
 import coracle
 import fu
-from churn_cases import (DOWN, FRESH, HEAVY_CHUNK, TILE_ROWS, TILE_SLOTS, UP, check_static, churn_python, cut, heavy_rows, hub60,
-                         live_np, random_masks, row_slots, scripted_run, star, tile_census, tile_limit_graph, tile_segment)
+from churn_cases import (DOWN, FRESH, HEAVY_CHUNK, TILE_ROWS, TILE_SLOTS, UP, byte_masks, check_static, chunk_edge_case,
+                         chunk_edge_graph, chunk_edge_topology, churn_python, cut, flapping_case, heavy_rows, hub60, live_np,
+                         random_masks, row_slots, scripted_run, star, tile_census, tile_limit_graph, tile_segment)
 from conftest import ca_sync_fixtures, load_npz
+from fu import _lib as L
 from parity_util import FAMILIES, assert_same_bits, count_neg_zero
 
 pytestmark = pytest.mark.gpu
@@ -332,3 +339,165 @@ def test_cli_bench_graph_with_churn(capsys):
     assert 1700 < alive < 1900
     assert line.startswith(f"graph n={g.n} E={g.E} ") and " rounds=7 " in line and line.endswith(f" alive={alive}")
     assert np.isfinite(float(line.split(" max_err=")[1].split()[0]))
+
+
+# ------------------------------------------------------------------------------------
+# 8. heavy rows at the chunk edges
+# ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["A", "B", "C"])
+def test_chunk_edge_static_topology_equals_ca_sync_on_the_live_subgraph(which):
+    """Rows of 2047, 2048, 2049, 4096 and 4097 slots under a topology set before round 0: "A" has
+    slots 0, 2047, 2048 and d-1 of the long rows DOWN, the 2048 row alive without a live slot and
+    the 2047 row dead; "B" one live slot in the 2049 row, the one of its second chunk, and the
+    second chunk of the 4096 row DOWN; "C" that slot as the 2049 row's only DOWN one and the middle
+    chunk of the 4097 row DOWN."""
+    g = chunk_edge_graph()
+    alive, up = chunk_edge_topology(which)
+    v = fu.uniform_values(g.n, seed=5)
+    live = live_np(*g.arrays(), alive, up)
+    with fu.CollectAllChurn(g, v) as eng:
+        eng.set_topology(alive, up)
+        assert eng.stats == (int(alive.sum()), int(live.sum()))
+        assert np.array_equal(eng.slot_state(), np.where(live, FRESH, DOWN))
+        for r in (1, 2, 5):
+            eng.run(r - eng.rounds_done)
+            check_static(g, alive, up, v, eng.estimates(), eng.flows(), eng.slot_state(), r, ("chunk edges", which, r))
+        assert eng.stats == (int(alive.sum()), int(live.sum()))
+
+
+@pytest.mark.parametrize("family", ["uniform", "subn", "special"])
+def test_chunk_edge_scripted_run_equals_the_python_restatement(family):
+    """run(3); topology "A"; run(1); run(2); half of the dead and of the cut links back; run(1);
+    run(2); reset; run(2), everything compared after every step: UP, DOWN and FRESH slots in one
+    chunk of every long row, slots that turn FRESH on both sides of a chunk boundary and in the
+    one-slot last chunks, heavy rows at both ends of a slot. "subn" brings -0.0 and "special" NaN
+    into the long rows' flows (tests/test_churn_case_inputs.py)."""
+    g, v, script, ref = chunk_edge_case(family)
+    with fu.CollectAllChurn(g, v) as eng:
+        _follow(eng, script, ref, ("chunk edges", family))
+        assert eng.rounds_done == 2
+
+
+# ------------------------------------------------------------------------------------
+# 9. a topology call before every round
+# ------------------------------------------------------------------------------------
+def test_flapping_topology_every_round():
+    """Ten times set_topology(fresh random masks); run(1) on tile_limit_graph(): slots that go
+    UP -> DOWN -> FRESH -> UP -> DOWN, topology calls on both parities of the double buffer (the
+    flow a call drops is the one the next round reads)."""
+    g, v, script, ref = flapping_case()
+    with fu.CollectAllChurn(g, v) as eng:
+        _follow(eng, script, ref, ("flapping",))
+        assert eng.rounds_done == len(script) // 2
+
+
+# ------------------------------------------------------------------------------------
+# 10. one node, no link, one link, more nodes than slots
+# ------------------------------------------------------------------------------------
+NO_I32 = np.zeros(0, dtype=np.int32)
+NO_U8 = np.zeros(0, dtype=np.uint8)
+
+
+def _u8(*x):
+    return np.array(x, dtype=np.uint8)
+
+
+def _follow_csr(rp, col, v, script, what):
+    """_follow on a handle made from the raw CSR; returns the restatement's Result."""
+    rev = fu.Graph.from_csr(rp, col).rev if len(col) else NO_I32
+    ref = churn_python(rp, col, rev, v, script)
+    with fu.CollectAllChurn(rowptr=rp, col=col, values=v) as eng:
+        assert eng.stats == (len(v), len(col)) and eng.slot_state().shape == (len(col),) and eng.flows().shape == (len(col),)
+        _follow(eng, script, ref, what)
+    return ref
+
+
+def test_one_node_without_a_link():
+    """n = 1, E = 0: set_topology with and without an alive array and with an empty link_up, the
+    node dead and alive again, reset, every readback."""
+    script = [("run", 2), ("topology", _u8(0), None), ("values", np.array([7.0])), ("run", 1), ("topology", None, NO_U8),
+              ("run", 1), ("topology", _u8(1), NO_U8), ("reset",), ("topology", None, None), ("run", 1), ("topology", _u8(0), NO_U8),
+              ("reset",), ("run", 2)]
+    ref = _follow_csr(np.zeros(2, dtype=np.int64), NO_I32, np.array([3.5]), script, ("n = 1",))
+    assert [float(s.a[0]) for s in ref.steps] == [3.5, 3.5, 3.5, 3.5, 3.5, 7.0, 7.0, 0.0, 0.0, 7.0, 7.0, 0.0, 0.0]
+    assert [s.alive_nodes for s in ref.steps][:5] == [1, 0, 0, 0, 1]
+
+
+def test_five_isolated_nodes_two_of_them_dead():
+    v = np.array([1.0, -2.5, -0.0, 1e300, 5e-324])
+    rp = np.zeros(6, dtype=np.int64)
+    alive = _u8(1, 0, 1, 0, 1)
+    script = [("topology", alive, None), ("run", 2), ("topology", _u8(0, 0, 1, 0, 1), NO_U8), ("values", v + 1.0), ("run", 1),
+              ("reset",), ("run", 1)]
+    ref = _follow_csr(rp, NO_I32, v, script, ("isolated",))
+    assert (ref.steps[0].alive_nodes, ref.steps[0].live_slots) == (3, 0)
+    assert_same_bits(ref.steps[1].a, np.array([1.0, 0.0, 0.0, 0.0, 5e-324]), "the dead keep 0.0")  # (-0.0 - 0.0) + 0.0 = +0.0
+    assert_same_bits(ref.steps[4].a, np.array([1.0, 0.0, 1.0, 0.0, 1.0]), "node 0 keeps its estimate")
+    with fu.CollectAllChurn(rowptr=rp, col=NO_I32, values=v) as eng:
+        eng.set_topology(alive)
+        assert eng.stats == (3, 0)
+        eng.run(3)
+        assert_same_bits(eng.estimates(), ref.steps[1].a, "isolated, the first topology")
+
+
+def test_two_nodes_and_one_link():
+    """Kill one end: the survivor fires v / 1. Revive it: the slot is FRESH, then UP. Cut the link
+    with both ends alive."""
+    rp, col = np.array([0, 1, 2], dtype=np.int64), np.array([1, 0], dtype=np.int32)
+    v = np.array([1.0, 4.0])
+    script = [("run", 2), ("topology", _u8(1, 0), None), ("run", 1), ("topology", _u8(1, 1), _u8(1, 1)), ("run", 1), ("run", 1),
+              ("topology", None, _u8(0, 0)), ("run", 2), ("topology", None, None), ("run", 1), ("reset",), ("run", 1)]
+    ref = _follow_csr(rp, col, v, script, ("one link",))
+    assert ref.steps[1].state.tolist() == [DOWN, DOWN] and ref.steps[2].a[0] == 1.0 and ref.steps[2].a[1] == ref.steps[0].a[1]
+    assert ref.steps[3].state.tolist() == [FRESH, FRESH] and ref.steps[4].state.tolist() == [UP, UP]
+    assert ref.steps[6].state.tolist() == [DOWN, DOWN] and ref.steps[6].alive_nodes == 2 and ref.steps[7].a.tolist() == [1.0, 4.0]
+    assert ref.steps[8].state.tolist() == [FRESH, FRESH]
+
+
+def test_more_nodes_than_slots():
+    """n = 1000 with the single link 998 - 999: the topology pass is sized by n, and the alive
+    nodes at ids >= E = 2 are counted by threads, and from 256 on by blocks, that hold no slot."""
+    n = 1000
+    g = fu.Graph.from_edges(n, np.array([998]), np.array([999]))
+    assert g.E == 2 < n
+    v = fu.uniform_values(n, seed=6)
+    a1, _ = random_masks(g, 0.3, 0.0, 61)
+    a2 = np.ones(n, dtype=np.uint8)
+    a2[256:] = random_masks(g, 0.3, 0.0, 62)[0][256:]
+    a3 = np.ones(n, dtype=np.uint8)
+    a3[:2] = 0
+    a4, _ = random_masks(g, 0.3, 0.0, 63, keep=(998, 999))
+    assert 600 < a1.sum() < 800 and a2[:256].all() and 0 < (a2 == 0).sum() and a4[998:].all()
+    script = [("topology", a1, None), ("run", 2), ("topology", a2, None), ("run", 1), ("topology", a3, _u8(1, 1)), ("run", 1),
+              ("topology", a4, None), ("run", 2), ("reset",), ("run", 1), ("topology", a4, _u8(0, 0)), ("run", 1)]
+    ref = churn_python(*g.arrays(), v, script)
+    assert [ref.steps[q].alive_nodes for q in (0, 2, 4, 6)] == [int(a.sum()) for a in (a1, a2, a3, a4)]
+    assert ref.steps[4].alive_nodes == n - 2 and ref.steps[6].live_slots == 2 and ref.steps[10].live_slots == 0
+    with fu.CollectAllChurn(g, v) as eng:
+        _follow(eng, script, ref, ("n > E",))
+
+
+# ------------------------------------------------------------------------------------
+# 11. mask bytes other than 0 and 1, through the C entry point
+# ------------------------------------------------------------------------------------
+def test_any_nonzero_mask_byte_is_on():
+    """fu_churn_set_topology called directly with alive bytes from {0, 1, 2, 128, 255} and link_up
+    bytes 7 on a slot and 255 on its reverse (fu.CollectAllChurn.set_topology would normalise
+    them): the counts, the states and 5 rounds are the restatement's under the same masks as
+    booleans."""
+    g = hub60()
+    v = fu.uniform_values(g.n, seed=3)
+    alive, up = byte_masks(g, 71)
+    script = [("run", 2), ("topology", alive != 0, up != 0), ("run", 5)]
+    ref = churn_python(*g.arrays(), v, script)
+    assert 0 < ref.steps[1].alive_nodes < g.n and 0 < ref.steps[1].live_slots < int((up != 0).sum())
+    with fu.CollectAllChurn(g, v) as eng:
+        eng.run(2)
+        assert L.lib.fu_churn_set_topology(eng._h, L.ptr(alive), L.ptr(up)) == 0, L.last_error()
+        assert eng.stats == (ref.steps[1].alive_nodes, ref.steps[1].live_slots)
+        assert np.array_equal(eng.slot_state(), ref.steps[1].state)
+        _check(eng, ref.steps[1].a, ref.steps[1].f, ("bytes", "after the call"))
+        for r in range(5):
+            eng.run(1)
+            _check(eng, ref.a_rounds[2 + r], ref.f_rounds[2 + r], ("bytes", "round", r))
+        assert np.array_equal(eng.slot_state(), ref.state)

@@ -30,10 +30,10 @@ import numpy as np
 import pytest
 
 import fu
-from err_cases import (ERR_BATCH_KS, ERR_DIST_HUB, ERR_DIST_MEGA, ERR_DIST_R, ERR_R, ERR_REDUCER_R, ERR_RMAT_HUB,
+from err_cases import (ERR_BATCH_KS, ERR_DIST_HUB, ERR_DIST_MEGA, ERR_DIST_R, ERR_GRID, ERR_R, ERR_REDUCER_R, ERR_RMAT_HUB,
                        ERR_RMAT_MEGA, ISO_TAILS, err_batch_case, err_batch_nonfinite_rows, err_batch_trace_probes,
-                       err_class_case, err_dist_case, err_isolated_case, err_rccl_case, err_rmat_case,
-                       err_scalar_reducer_case)
+                       err_churn_reducer_case, err_class_case, err_dist_case, err_isolated_case, err_rccl_case,
+                       err_rmat_case, err_scalar_reducer_case, with_decoys)
 from parity_util import CLASS_EDGE_DEGREES, assert_same_bits, planted_D, planted_targets
 
 pytestmark = pytest.mark.gpu
@@ -256,6 +256,47 @@ def test_fu_max_err_stride_loop(layout):
         t, want, _ = planted_targets(a_rounds, p, D)
         eng.set_targets(t)
         assert_same_bits(np.array([eng.max_err()]), want[-1:], (layout, f"probe {p}"))
+    eng.close()
+
+
+def test_kc_max_err_stride_loop_skips_the_dead():
+    """kc_max_err, the churn engine's reduction over the alive nodes, on n = 300,000 > 1024 x 256
+    with a tenth of the nodes dead: the argmax at the probes of test_fu_max_err_stride_loop, one
+    at a time, while a dead node of block 0, one of the last block of the first stride and one
+    of the second stride each sit 2^20 D off their targets. The whole trace and max_err, by bits;
+    then a NaN target on an alive node of the second stride, and NaN and inf on the dead."""
+    g, v, alive, a_rounds, probes, decoys = err_churn_reducer_case()
+    last, D = a_rounds[-1], planted_D(a_rounds)
+    eng = fu.CollectAllChurn(g, v)
+    eng.set_topology(alive, None)
+    assert eng.stats[0] == int(alive.sum())
+    eng.set_targets(with_decoys(last, last, decoys, D))
+    tr = eng.run(ERR_REDUCER_R, err_every=1)
+    assert_same_bits(tr, _zero_trace(a_rounds), "no probe, the decoys only")
+    assert _is_pos_zero(tr) and _is_pos_zero(eng.max_err())
+    assert_same_bits(eng.estimates(), last, "estimates")
+    for p in probes:
+        t, want, runner_up = planted_targets(a_rounds, p, D)
+        eng.reset()
+        eng.set_targets(with_decoys(t, last, decoys, D))
+        tr = eng.run(ERR_REDUCER_R, err_every=1)
+        assert_same_bits(tr, want, (f"probe {p}", f"without its row: {runner_up.tolist()}"))
+        assert_same_bits(np.array([eng.max_err()]), want[-1:], (f"probe {p}", "max_err"))
+    t, want, _ = planted_targets(a_rounds, probes[0], D)
+    for bad in (np.nan, np.inf):
+        for q in decoys:
+            tq = with_decoys(t, last, decoys, D)
+            tq[q] = bad
+            eng.set_targets(tq)
+            assert_same_bits(np.array([eng.max_err()]), want[-1:], (bad, "on the dead node", q))
+    tq = with_decoys(t, last, decoys, D)
+    tq[probes[4]] = np.nan
+    assert probes[4] == ERR_GRID * 256 and alive[probes[4]]
+    eng.set_targets(tq)
+    assert_same_bits(np.array([eng.max_err()]), np.array([np.nan]), "NaN on an alive node of the second stride")
+    eng.reset()
+    eng.set_targets(tq)
+    assert_same_bits(eng.run(ERR_REDUCER_R, err_every=1), np.full(ERR_REDUCER_R, np.nan), "NaN trace")
     eng.close()
 
 

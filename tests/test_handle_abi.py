@@ -1,12 +1,12 @@
-"""The handle scaffold the batched, lossy and pairwise engines share (fu_batch_*, fu_lossy_*,
-fu_pair_*), without a GPU: every argument and graph check runs before the first HIP call, so
-each bad input below returns its code and leaves its text in fu_last_error() on any host. One
-table, looped over the three engines; the texts are the library's, written out in full, the
-function-name prefix included.
+"""The handle scaffold the batched, lossy, pairwise and churn engines share (fu_batch_*,
+fu_lossy_*, fu_pair_*, fu_churn_*), without a GPU: every argument and graph check runs before the
+first HIP call, so each bad input below returns its code and leaves its text in fu_last_error()
+on any host. One table, looped over the four engines; the texts are the library's, written out in
+full, the function-name prefix included.
 
 The engines differ in one check on purpose: fu_batch_create only asks that rev[k] lie in the
-neighbour's row at a slot that points back (its kernels never read rev), while fu_lossy_create
-and fu_pair_create also ask for an involution (theirs gather through it).
+neighbour's row at a slot that points back (its kernels never read rev), while fu_lossy_create,
+fu_pair_create and fu_churn_create also ask for an involution (theirs gather through it).
 test_batch_keeps_its_symmetric_only_rev_check pins that difference on a doubled edge."""
 import ctypes
 import math
@@ -17,7 +17,7 @@ import pytest
 import fu
 from fu import _lib as L
 
-ENGINES = ("batch", "lossy", "pair")
+ENGINES = ("batch", "lossy", "pair", "churn")
 ARG, HIP, GRAPH = -1, -2, -5
 NULL = object()  # "pass a null pointer here"
 
@@ -159,7 +159,7 @@ def test_batch_keeps_its_symmetric_only_rev_check():
     at a slot that points back, which is all fu_batch_create asks; rev[rev[1]] = 0 != 1, so it
     is no involution, and the engines that gather through rev refuse it at edge 1."""
     _past_validation("batch", _create("batch", DOUBLED_RP, DOUBLED_COL, DOUBLED_REV))
-    for eng in ("lossy", "pair"):
+    for eng in ("lossy", "pair", "churn"):
         assert _create(eng, DOUBLED_RP, DOUBLED_COL, DOUBLED_REV) == (GRAPH, f"fu_{eng}_create: {_REV}1"), eng
         # the pairing the library builds itself goes through the same check: it looks a
         # neighbour up by id, so on a doubled edge it is no involution either
@@ -173,7 +173,8 @@ SHARED = {"destroy": (), "reset": (), "set_targets": (None,), "run": (1, 0, None
 OWN = {"batch": {},
        "lossy": {"set_values": (None,), "get_stats": (None,), "set_loss": (0.5, 1), "set_link_mask": (None,)},
        "pair": {"set_values": (None,), "get_stats": (None,), "set_seed": (1,), "set_option": (b"match", 1),
-                "get_cache": (None,)}}
+                "get_cache": (None,)},
+       "churn": {"set_values": (None,), "get_stats": (None,), "set_topology": (None, None), "get_slot_state": (None,)}}
 
 
 @pytest.mark.parametrize("eng", ENGINES)

@@ -1,11 +1,14 @@
-"""The handle scaffold the batched, lossy and pairwise engines share, on the GPU: the run loop
-with its error-trace slots, the timed loop, reset, the state errors of a live handle and the
+"""The handle scaffold the batched, lossy, pairwise and churn engines share, on the GPU: the run
+loop with its error-trace slots, the timed loop, reset, the state errors of a live handle and the
 teardown, each engine against its own restatement (coracle.ca_sync / ca_rounds per column,
-lossy_cases.oracle_lossy, pair_cases.oracle_pair), by bit pattern.
+lossy_cases.oracle_lossy, pair_cases.oracle_pair, churn_cases.churn_python), by bit pattern.
 
 Two golden graphs: ca_sync_er300_m450 (light rows only) and ca_sync_star_257, whose hub is above
-every engine's heavy threshold (64, 128 and 64 slots), so both launch classes of every engine
-run. The batch has K = 3 columns: an error width that is neither 1 nor a divisor of 256."""
+every engine's heavy threshold (64, 128, 64 and 128 slots), so both launch classes of every
+engine run. The batch has K = 3 columns: an error width that is neither 1 nor a divisor of 256.
+The churn handle runs under a fixed topology with a fifth of the nodes dead and a tenth of the
+links down (star_257's hub alive), applied when it is made; its error trace is the maximum over
+the alive nodes."""
 import functools
 import math
 
@@ -14,6 +17,7 @@ import pytest
 
 import coracle
 import fu
+from churn_cases import churn_python, random_masks
 from conftest import ca_sync_fixtures, load_npz
 from fu import _lib as L
 from lossy_cases import hashed, oracle_lossy
@@ -22,7 +26,7 @@ from parity_util import FAMILIES, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
-ENGINES = ("batch", "lossy", "pair")
+ENGINES = ("batch", "lossy", "pair", "churn")
 GRAPHS = ("er300_m450", "star_257")
 SEED, LOSS, K = 11, 0.25, 3
 R_FIT, R_GROW, R_TIMED = 4, 12, 3  # run(4, err_every=4); run(12, err_every=1); run_timed(3)
@@ -52,6 +56,13 @@ def _targets(eng, name):
 
 
 @functools.lru_cache(maxsize=None)
+def _topology(name):
+    """The churn handle's (alive, link_up): the hub of the star stays alive."""
+    g, _ = _graph(name)
+    return random_masks(g, 0.2, 0.1, SEED, keep=(int(np.argmax(g.degrees)),) if name == "star_257" else ())
+
+
+@functools.lru_cache(maxsize=None)
 def _ref(eng, name):
     """(a_rounds, state): the estimates after each of rounds 0 .. R-1, and what the handle holds
     after R rounds, from the oracle alone."""
@@ -73,6 +84,9 @@ def _ref(eng, name):
     if eng == "lossy":
         a, f, sn = oracle_lossy(*g.arrays(), v, R, hashed(LOSS, SEED, g.E), snaps=tuple(range(R)))
         return np.stack([sn[r] for r in range(R)]), {"estimates": a, "flows": f}
+    if eng == "churn":
+        ref = churn_python(*g.arrays(), v, [("topology",) + _topology(name)] + [("run", 1)] * R)
+        return np.stack(ref.a_rounds), {"estimates": ref.a, "flows": ref.f}
     last, f, c, sn = oracle_pair(*g.arrays(), v, R, SEED, snaps=tuple(range(R)))
     return np.stack([sn[r] for r in range(R)]), {"estimates": last, "flows": f, "cache": c}
 
@@ -84,6 +98,10 @@ def _make(eng, name):
         return fu.CollectAllBatch(g, v)
     if eng == "lossy":
         return fu.CollectAllLossy(g, v, loss=LOSS, seed=SEED)
+    if eng == "churn":
+        h = fu.CollectAllChurn(g, v)
+        h.set_topology(*_topology(name))
+        return h
     return fu.PairwiseSync(g, v, seed=SEED)
 
 
@@ -96,7 +114,8 @@ def _state(eng, h):
 
 def _want_trace(eng, name, rounds):
     a_rounds, t = _ref(eng, name)[0], _targets(eng, name)
-    return np.stack([np.max(np.abs(a_rounds[r - 1] - t), axis=0) for r in rounds])
+    on = _topology(name)[0] != 0 if eng == "churn" else slice(None)  # a dead node's frozen estimate does not count
+    return np.stack([np.max(np.abs(a_rounds[r - 1] - t)[on], axis=0) for r in rounds])
 
 
 def _same_state(got, want, what):
@@ -160,7 +179,8 @@ def test_live_handle_state_errors(eng):
 
 
 @pytest.mark.parametrize("first,second,third", [("batch", "lossy", "pair"), ("lossy", "pair", "batch"),
-                                                ("pair", "batch", "lossy")])
+                                                ("pair", "batch", "lossy"), ("churn", "pair", "lossy"),
+                                                ("lossy", "churn", "batch"), ("batch", "pair", "churn")])
 def test_handles_close_in_the_opposite_order_of_creation(first, second, third):
     """Two engines on one graph, each closed after a run, the later one first; the earlier one
     is unharmed by it, and a handle of the third engine made afterwards matches the oracle."""

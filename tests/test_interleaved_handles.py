@@ -5,9 +5,10 @@ rounds. Creating, running, resetting, reading back and destroying a handle must 
 handle's bits alone.
 
 Each handle is compared with its own reference (coracle.ca_sync, lossy_cases.oracle_lossy,
-pair_cases.oracle_pair, coracle.replay), never with another handle, by bit pattern. The graphs are
-ER(6000, 24000) and RMAT(12, 16): small enough for cheap references, with heavy rows, several
-tiles and more than one block per XCD slot. At most 8 handles are open at any time; everything
+pair_cases.oracle_pair, churn_cases.churn_python, coracle.replay), never with another handle, by
+bit pattern. The graphs are ER(6000, 24000) and RMAT(12, 16): small enough for cheap references,
+with heavy rows, several tiles and more than one block per XCD slot; the churn handle, whose
+reference is Python, runs on lossy_cases.tile_limit_graph() (2641 nodes, one heavy row). At most 8 handles are open at any time; everything
 runs in this process."""
 import functools
 
@@ -16,6 +17,7 @@ import pytest
 
 import coracle
 import fu
+from churn_cases import churn_python, random_masks, tile_limit_graph, tile_segment
 from lossy_cases import hashed, oracle_lossy
 from pair_cases import oracle_pair
 from parity_util import FAMILIES, assert_same_bits
@@ -68,7 +70,10 @@ def _check_batch(eng, refs, what):
 def test_four_engine_types_round_robin():
     """CollectAll (stage, RMAT), CollectAllBatch (K = 2, ER), CollectAllLossy (p = 0.25, RMAT) and
     PairwiseSync (ER), each with values of its own: run(1) on each in turn, 12 turns, with no
-    synchronize() in between; then every handle equals its own reference after 12 rounds."""
+    synchronize() in between; then every handle equals its own reference after 12 rounds. A
+    CollectAllChurn handle (tile_limit_graph) takes the fifth place in every turn, with a
+    set_topology (which waits for its own stream only) between its turns 4 and 5 and another
+    between 9 and 10."""
     rounds = 12
     er, rmat = _er(), _rmat()
     one = _ca_ref("rmat", "sym", 1, rounds)
@@ -81,11 +86,20 @@ def test_four_engine_types_round_robin():
     batch = fu.CollectAllBatch(er, np.stack([c[0] for c in cols], axis=1))
     lossy = fu.CollectAllLossy(rmat, v_lossy, loss=LOSS, seed=SEED)
     pair = fu.PairwiseSync(er, v_pair, seed=SEED)
+    tg = tile_limit_graph()
+    v_churn = FAMILIES["sym"](tg.n, seed=6)
+    topo = {5: random_masks(tg, 0.2, 0.1, 31, keep=(tile_segment("heavy")[0],)), 10: random_masks(tg, 0.1, 0.2, 32)}
+    script = [("run", 5), ("topology",) + topo[5], ("run", 5), ("topology",) + topo[10], ("run", 2)]
+    churn_ref = churn_python(*tg.arrays(), v_churn, script)
+    churn = fu.CollectAllChurn(tg, v_churn)
     engines = (ca, batch, lossy, pair)
-    for _ in range(rounds):
+    for turn in range(rounds):
         for eng in engines:
             eng.run(1)
-    assert [eng.rounds_done for eng in engines] == [rounds] * 4
+        if turn in topo:
+            churn.set_topology(*topo[turn])
+        churn.run(1)
+    assert [eng.rounds_done for eng in engines] == [rounds] * 4 and churn.rounds_done == rounds
     _check_ca(ca, one, ("CollectAll",))
     _check_batch(batch, cols, ("CollectAllBatch",))
     assert_same_bits(lossy.estimates(), lossy_ref[0], "CollectAllLossy estimates")
@@ -93,7 +107,11 @@ def test_four_engine_types_round_robin():
     assert_same_bits(pair.estimates(), pair_ref[0], "PairwiseSync last")
     assert_same_bits(pair.flows(), pair_ref[1], "PairwiseSync flows")
     assert_same_bits(pair.cache(), pair_ref[2], "PairwiseSync cache")
-    for eng in engines:
+    assert_same_bits(churn.estimates(), churn_ref.a, "CollectAllChurn estimates")
+    assert_same_bits(churn.flows(), churn_ref.f, "CollectAllChurn flows")
+    assert np.array_equal(churn.slot_state(), churn_ref.state)
+    assert churn.stats == (churn_ref.steps[-1].alive_nodes, churn_ref.steps[-1].live_slots)
+    for eng in engines + (churn,):
         eng.close()
 
 

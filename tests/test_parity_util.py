@@ -8,10 +8,10 @@ import pytest
 
 import coracle
 import oracle
-from err_cases import (ERR_BATCH_KS, ERR_DIST_CASES, ERR_RMAT_HUB, ERR_RMAT_MEGA, LIGHT_TILE_GEOMETRIES,
-                       PLANTED_CASES, dist_thresholds, err_batch_case, err_batch_nonfinite_rows, err_class_case,
-                       err_dist_case, err_isolated_case, err_rmat_case, light_tiles, planted_conditions,
-                       rows_with_ghosts)
+from err_cases import (ERR_BATCH_KS, ERR_CHURN_DECOY, ERR_DIST_CASES, ERR_GRID, ERR_RMAT_HUB, ERR_RMAT_MEGA,
+                       LIGHT_TILE_GEOMETRIES, PLANTED_CASES, dist_thresholds, err_batch_case, err_batch_nonfinite_rows,
+                       err_churn_reducer_case, err_class_case, err_dist_case, err_isolated_case, err_rmat_case,
+                       light_tiles, planted_conditions, rows_with_ghosts, with_decoys)
 from parity_util import (CLASS_EDGE_DEGREES, FAMILIES, assert_same_bits, count_neg_zero, planted_D,
                          planted_targets)
 
@@ -150,6 +150,28 @@ def test_planted_inputs_have_a_unique_maximum(case):
         _, want, runner_up = planted_targets(a, p, D)
         assert np.all(runner_up < want) and runner_up[-1] == 0.0
         assert abs(want[-1] - D) <= D * 2.0 ** -40  # D itself, up to the rounding of a + D
+
+
+def test_churn_reducer_decoys_are_dead_where_named():
+    """kc_max_err's case: the probes are alive, the three decoys dead, one in block 0, one in
+    the last block of the first stride (1024 blocks of 256) and one in the second stride; about a
+    tenth of the nodes are dead and stay at 0.0; D exceeds every honest error, and the decoys'
+    2^20 D would be the maximum if a dead node entered it."""
+    g, v, alive, a, probes, decoys = err_churn_reducer_case()
+    stride = ERR_GRID * 256
+    assert g.n > stride and probes == [0, 255, 256, stride - 1, stride, g.n - 1]
+    assert alive[probes].all() and not alive[decoys].any()
+    assert 0 <= decoys[0] < 256 and stride - 256 <= decoys[1] < stride <= decoys[2] < g.n
+    assert 0.08 < 1.0 - alive.mean() < 0.12
+    assert not a[:, alive == 0].any() and (a[-1][alive != 0] != 0.0).all()
+    D = planted_D(a)
+    assert D > 2.0 * np.max(np.abs(a - a[-1]))
+    for p in probes:
+        t, want, _ = planted_targets(a, p, D)
+        td = with_decoys(t, a[-1], decoys, D)
+        assert np.array_equal(np.flatnonzero(td != t), decoys)
+        assert np.all(np.abs(a[:, decoys] - td[decoys]) == ERR_CHURN_DECOY * D) and np.all(want < ERR_CHURN_DECOY * D)
+        assert_same_bits(np.max(np.abs(a - td)[:, alive != 0], axis=1), want)
 
 
 def test_planted_cases_cover_what_they_name():
