@@ -61,11 +61,33 @@ def _seed_at(seed, r):
     return int(seed(r) if callable(seed) else seed)
 
 
+class Recorded:
+    """In place of a seed: the matching of every round as recorded arrays mate[r][i] and
+    initiator[r][i] (tests/golden/rule_pair_hub_mix.npz), so that no hash is evaluated."""
+
+    def __init__(self, mate, initiator):
+        self.mate, self.initiator = np.asarray(mate), np.asarray(initiator)
+
+    def pairs(self, rowptr, col, rev, r):
+        """[(i, s, j, t)] of round r, by listener; s is where j stands in row i (rows hold a
+        neighbour once)."""
+        out = []
+        for j in np.flatnonzero((self.mate[r] >= 0) & (self.initiator[r] == 0)):
+            i = int(self.mate[r][j])
+            assert self.initiator[r][i] and int(self.mate[r][i]) == j
+            (s,) = np.flatnonzero(col[rowptr[i]:rowptr[i + 1]] == j)
+            out.append((i, int(s), int(j), int(rev[rowptr[i] + s]) - int(rowptr[j])))
+        return out
+
+
 def pairs_of_round(rowptr, col, rev, seed, r):
     """[(i, s, j, t)] of round r, by listener: i fires on its slot s, j answers on its slot t.
-    From matching_py; the slot is the proposer's pick, restated here."""
+    From matching_py; the slot is the proposer's pick, restated here. A `Recorded` in place of
+    the seed gives its own pairs."""
     rp = np.asarray(rowptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int32)
+    if isinstance(seed, Recorded):
+        return seed.pairs(rp, col, rev, r)
     sd = _seed_at(seed, r)
     k = (rp.tobytes(), col.tobytes(), sd, r)
     if k not in _MATCHINGS:

@@ -501,3 +501,33 @@ def test_any_nonzero_mask_byte_is_on():
             eng.run(1)
             _check(eng, ref.a_rounds[2 + r], ref.f_rounds[2 + r], ("bytes", "round", r))
         assert np.array_equal(eng.slot_state(), ref.state)
+
+
+# ------------------------------------------------------------------------------------
+# 12. the rule itself: the reference's Peers through the recorded topologies (tests/golden/)
+# ------------------------------------------------------------------------------------
+def test_reference_peers_through_recorded_topologies():
+    """hub_mix (rows of 2101 and 130 slots, light tiles, isolated rows): rounds 0-7 all alive,
+    topologies before rounds 8, 16 and 24, run from stop to stop. Estimates and flows are what the
+    reference's own on_receive / tick / avg_and_send left (make_golden.ca_churn_sync, neighbours
+    kept in row order); the slot states are the entries that driver created and dropped.
+    The values are in [0, 100), so no estimate is -0.0: a FRESH slot that gathered -f_old[rev k]
+    (-0.0, the dropped flow) would leave every bit here as it is; the subnormal family of
+    test_chunk_edge_scripted_run_equals_the_python_restatement is what sees that."""
+    import rule_cases
+
+    d = rule_cases.load("churn")
+    after_event = rule_cases.churn_states_after_events(d)
+    with fu.CollectAllChurn(rowptr=d.rowptr, col=d.col, rev=d.rev, values=d.values) as eng:
+        assert np.array_equal(eng.slot_state(), after_event[0])
+        for q, stop in enumerate(d.stops):
+            if q:
+                eng.set_topology(d.alive[q], d.link_up[q])
+                assert d.event_rounds[q] == eng.rounds_done
+                assert np.array_equal(eng.slot_state(), after_event[q]), ("after the event before round", eng.rounds_done)
+            counts = (int((d.alive[q] != 0).sum()), int(d.live[q].sum()))
+            assert eng.stats == counts, stop
+            eng.run(stop - eng.rounds_done)
+            _check(eng, d.last_avg[q], d.flows[q], ("reference peers", "after", stop))
+            assert np.array_equal(eng.slot_state(), np.where(d.live[q], UP, DOWN)), stop
+            assert eng.stats == counts, stop

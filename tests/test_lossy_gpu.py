@@ -353,3 +353,23 @@ def test_outage_of_a_whole_full_tile():
             assert eng.stats == (g.E * (r - 1), _lost(g, delivered, r)), r
     a2, _, _ = oracle_lossy(*g.arrays(), v, 9, plain)
     assert not np.array_equal(a, a2)
+
+
+# ------------------------------------------------------------------------------------
+# 10. the rule itself: the reference's Peers under the recorded loss (tests/golden/)
+# ------------------------------------------------------------------------------------
+def test_reference_peers_under_recorded_loss():
+    """hub_mix (rows of 2101 and 130 slots, light tiles, isolated rows) at the recorded (p, seed)
+    and link mask, run from stop to stop: estimates and flows are what the reference's own
+    on_receive / tick / avg_and_send left (make_golden.ca_lossy_sync), and the lost counter is
+    the number of slots the recording marks lost."""
+    import rule_cases
+
+    d = rule_cases.load("lossy")
+    with fu.CollectAllLossy(rowptr=d.rowptr, col=d.col, rev=d.rev, values=d.values) as eng:
+        eng.set_loss(d.loss, d.seed)
+        eng.set_link_mask(d.down)
+        for q, stop in enumerate(d.stops):
+            eng.run(stop - eng.rounds_done)
+            _check(eng, d.last_avg[q], d.flows[q], ("reference peers", "after", stop))
+            assert eng.stats == (d.E * (stop - 1), rule_cases.lost_before(d, stop)), stop

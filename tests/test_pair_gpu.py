@@ -312,3 +312,22 @@ def test_listener_on_the_only_slot_of_its_second_chunk(match):
             eng.run(r - eng.rounds_done)
             _check(eng, oracle_pair(*g.arrays(), v, r, LAST_SLOT_SEED), ("match", match, "round", r))
         assert eng.stats[0] == pair_count(*g.arrays(), LAST_SLOT_SEED, LAST_SLOT_ROUNDS)
+
+
+# ------------------------------------------------------------------------------------
+# the rule itself: the reference's Peers over the recorded matching (tests/golden/)
+# ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("match", MATCHERS)
+def test_reference_peers_over_recorded_matching(match):
+    """hub_mix (rows of 2101 and 130 slots among rows of at most 7) at the recorded seed, run from
+    stop to stop: last averages, flows and caches are what the reference's own avg_and_send /
+    on_receive left (make_golden.pw_sync), and the pair counter is the recorded matching's."""
+    import rule_cases
+
+    d = rule_cases.load("pair")
+    with fu.PairwiseSync(rowptr=d.rowptr, col=d.col, rev=d.rev, values=d.values, seed=d.seed) as eng:
+        eng.set_option("match", match)
+        for q, stop in enumerate(d.stops):
+            eng.run(stop - eng.rounds_done)
+            _check(eng, (d.last_avg[q], d.flows[q], d.estimates[q]), ("reference peers", "match", match, "after", stop))
+            assert eng.stats[0] == int(d.initiator[:stop].sum()), stop
