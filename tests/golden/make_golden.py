@@ -32,6 +32,13 @@ messages arrive), `pw_sync` (the pairwise exchange over a recorded matching) and
 come from the engines' host-only helpers (`fu.lossy_delivered`, `fu.pair_matching`; no GPU), so
 libfu.so must be built.
 
+A last stage, `value_domain_fixtures`, sends signed zeros, subnormals, values that overflow and
+non-finite inputs through all of these drivers (vd_*.npz; manifest key "value_domain"): the
+families subn, huge, wide, special and special_off through `ca_sync` on hub_mix, subn and special
+through the three rule drivers on the recorded masks, matchings and topologies, and planted values
+through `tick_emulation` on the asym12 and rr32_d4 actors. Every float in those files is stored as
+its bit pattern. `--only-value-domain` runs that stage alone on the files of the earlier ones.
+
 The reference adds with the builtin `sum` (CA:106, PW:103). From CPython 3.12 on that sum is
 compensated and no longer the left-to-right chain, so the script writes nothing there.
 
@@ -444,13 +451,14 @@ def pw_sync(rowptr, col, values, mates, initiators, stops, seed):
 # ----------------------------------------------------------------------------------------
 # Tick-level emulation of Peer.loop
 # ----------------------------------------------------------------------------------------
-def tick_emulation(mode, actors, ticks, order, track_flows=False):
+def tick_emulation(mode, actors, ticks, order, track_flows=False, log_payloads=False):
     """Drive reference Peers through the emulated SimGrid loop for ticks 0..ticks-1.
 
     actors: list of (host_name, value_str, neighbours_str) in deployment order.
     Returns a dict with per-tick snapshots (after every actor acted at that tick) of
     global_values['last_avg'] (as ordered key/value lists), the event log, the final
     neighbour order per actor, final flows/estimates and fire counts.
+    log_payloads adds "recv_payloads": (flow, estimate) of every receive event, in event order.
     """
     mod, sg = load_reference(CA_FILE if mode == "ca" else PW_FILE)
     names = [a[0] for a in actors]
@@ -464,6 +472,7 @@ def tick_emulation(mode, actors, ticks, order, track_flows=False):
     fifo = [deque() for _ in range(n)]
     comm = [None] * n  # None | [matched: bool, payload, match_tick]
     events = []  # (tick, actor, kind, other): kind 0 = receive (other = sender), 1 = fire (other = neighbour or -1)
+    payloads = []  # (event index, flow, estimate) of every receive
     cur = {"t": 0}
 
     def router(dst, payload, size):
@@ -510,6 +519,7 @@ def tick_emulation(mode, actors, ticks, order, track_flows=False):
                 msg = c[1]
                 comm[i] = None
                 if type(msg) is mod.FlowUpdatingMsg:
+                    payloads.append((len(events), msg.flow, msg.estimate))
                     events.append((t, i, 0, aidx[msg.sender]))
                     peers[i].on_receive(msg)
             peers[i].tick()
@@ -530,6 +540,8 @@ def tick_emulation(mode, actors, ticks, order, track_flows=False):
         "errors_logged": World.errors,
         "queued_at_end": [len(q) for q in fifo],
     }
+    if log_payloads:
+        res["recv_payloads"] = payloads
     return res
 
 
@@ -743,6 +755,232 @@ def engine_rule_fixtures(manifest):
           flows=np.stack([bits(res[s][1]) for s in CHURN_STOPS]))
 
 
+# ----------------------------------------------------------------------------------------
+# The fp64 value domain: signed zeros, subnormals, overflow order, NaN placement
+# ----------------------------------------------------------------------------------------
+VD_SEED = 20261020
+VD_ROUNDS = (0, 2, 7, 16)  # round key r = index of the last round run: r + 1 rounds, as in ca_sync_*.npz
+VD_CA_FAMILIES = ("subn", "huge", "wide", "special", "special_off")
+VD_RULE_FAMILIES = ("subn", "special")
+VD_TICKS, VD_TICK_ORDER = 120, "rand:11"
+NEG_ZERO = np.uint64(1 << 63)
+
+
+def components(rowptr, col):
+    """Component label (the smallest node id of the component) per node."""
+    n = len(rowptr) - 1
+    lab = np.full(n, -1, dtype=np.int64)
+    for s in range(n):
+        if lab[s] >= 0:
+            continue
+        lab[s] = s
+        todo = [s]
+        while todo:
+            i = todo.pop()
+            for c in col[rowptr[i]:rowptr[i + 1]]:
+                if lab[c] < 0:
+                    lab[c] = s
+                    todo.append(int(c))
+    return lab
+
+
+def vd_counts(x):
+    """[-0.0, +inf, -inf, NaN] counts of a float64 array."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    return [int((x.view(np.uint64) == NEG_ZERO).sum()), int(np.isposinf(x).sum()), int(np.isneginf(x).sum()),
+            int(np.isnan(x).sum())]
+
+
+def vd_hub_leaf(rowptr, col, churn_alive):
+    """The first node adjacent to node 0 alone that the churn fixture kills before round 8: its
+    one slot is down in rounds 8-23 and FRESH before round 24."""
+    deg = np.diff(rowptr)
+    for i in range(131, 2102):
+        if deg[i] == 1 and col[rowptr[i]] == 0 and churn_alive[1][i] == 0:
+            return i
+    raise AssertionError("no dead hub leaf")
+
+
+def vd_values(family, rowptr, col, churn_alive):
+    """(values[n], planted[]) of a family on hub_mix. planted: the nodes whose input the family
+    sets by hand (special, special_off), or whose input is a zero (subn); empty otherwise.
+
+    special: uniform [0, 100) with -0.0, +inf, -inf and NaN on the four nodes of the two two-node
+    components outside node 0's (-0.0 beside +inf, -inf beside NaN), -0.0, 5e-324, -5e-324, +inf and NaN on the
+    isolated nodes 2350 .. 2354, and +inf on a node whose only neighbour is node 0. special_off is
+    special without that last +inf: nothing non-finite in node 0's component."""
+    n = len(rowptr) - 1
+    k = ("subn", "huge", "wide", "special").index("special" if family == "special_off" else family)
+    rng = np.random.default_rng(VD_SEED + k)
+    none = np.zeros(0, dtype=np.int32)
+    if family == "subn":
+        m = rng.integers(-50, 50, n)
+        v = m * 5e-324
+        zeros = np.flatnonzero(m == 0)
+        v[zeros[::2]] = -0.0
+        return v, zeros.astype(np.int32)
+    if family == "huge":
+        return rng.uniform(-1.0, 1.0, n) * 1.7e308, none
+    if family == "wide":
+        return rng.choice([-1.0, 1.0], n) * 2.0 ** rng.uniform(-60.0, 60.0, n), none
+    v = rng.random(n) * 100.0
+    lab = components(rowptr, col)
+    deg = np.diff(rowptr)
+    small = sorted((int(i) for i in range(n) if lab[i] != lab[0] and deg[i] >= 1), key=lambda i: (lab[i], i))
+    assert len(small) == 4 and not deg[2350:2355].any()  # hub_mix has two such components, of two nodes each
+    planted = {}
+    for i, x in zip(small, (-0.0, np.inf, -np.inf, np.nan)):
+        planted[i] = x
+    for i, x in zip(range(2350, 2355), (-0.0, 5e-324, -5e-324, np.inf, np.nan)):
+        planted[i] = x
+    if family == "special":
+        planted[vd_hub_leaf(rowptr, col, churn_alive)] = np.inf
+    for i, x in planted.items():
+        v[i] = x
+    return v, np.array(sorted(planted), dtype=np.int32)
+
+
+def vd_check_ca(family, rowptr, col, v, planted, la, fl):
+    """The conditions on the reference's output that tests/test_value_domain_golden.py asserts
+    again from the files. la[stop][n], fl[stop][E] in the order of VD_ROUNDS."""
+    if family == "subn":
+        assert vd_counts(la[-1])[0] >= 1 and vd_counts(fl[-1])[0] >= 1, "subn: no -0.0 at the last stop"
+    elif family == "huge":
+        assert np.isposinf(fl).any() and np.isneginf(fl).any() and np.isnan(la).any(), "huge: no +-inf flow or NaN estimate"
+    elif family in ("special", "special_off"):
+        assert np.isnan(la[-1]).any(), "special: no NaN at the last stop"
+        iso = [int(i) for i in planted if rowptr[i] == rowptr[i + 1] and bits(v[i:i + 1])[0] == NEG_ZERO]
+        assert iso, "special: no isolated node with input -0.0"
+        if family == "special":
+            leaf = [int(i) for i in planted if rowptr[i + 1] - rowptr[i] == 1 and col[rowptr[i]] == 0]
+            assert leaf and np.isposinf(v[leaf[0]]) and not np.isfinite(la[1:, 0]).any() and np.isfinite(la[0, 0]), \
+                "special: the hub-leaf inf does not reach row 0"
+        else:
+            assert np.isfinite(la[-1]).sum() >= 1000, "special_off: fewer than 1000 finite estimates at the last stop"
+
+
+def value_domain_fixtures(manifest):
+    """Signed zeros, subnormals, overflow and non-finite inputs through every driver above, on the
+    graphs, masks, matchings and topologies of the fixtures written before. Every float array is
+    stored as uint64 bit patterns, inputs included."""
+    rule = {k: np.load(os.path.join(HERE, manifest["engine_rules"][k]["file"])) for k in ("lossy", "pair", "churn")}
+    rowptr, col, rev = (rule["lossy"][k] for k in ("rowptr", "col", "rev"))
+    n, E = len(rowptr) - 1, len(col)
+    churn_alive = rule["churn"]["alive"]
+    out = manifest["value_domain"] = {"rounds_key": "ca files: rounds[k] = r is the state after r + 1 rounds; rule files: "
+                                      "stops[k] = s is the state after s rounds, as in the rule file",
+                                      "counts": "[-0.0, +inf, -inf, NaN] in the reference's estimates / flows per stop",
+                                      "ca": {}, "rule": {}, "tick": {}}
+
+    def write(fn, **arrays):
+        path = os.path.join(HERE, fn)
+        save_npz(path, **arrays)
+        size = os.path.getsize(path)
+        assert size <= MAX_FIXTURE_BYTES, (fn, size)
+        print("value domain", fn, size, "bytes")
+
+    def counts(stops, la, fl):
+        return {str(int(s)): {"estimates": vd_counts(la[q]), "flows": vd_counts(fl[q])} for q, s in enumerate(stops)}
+
+    # ---- collect-all: one file per family
+    for family in VD_CA_FAMILIES:
+        v, planted = vd_values(family, rowptr, col, churn_alive)
+        res = ca_sync(rowptr, col, v, VD_ROUNDS, seed=VD_SEED)
+        la = np.stack([res[r][0] for r in VD_ROUNDS])
+        fl = np.stack([res[r][1] for r in VD_ROUNDS])
+        vd_check_ca(family, rowptr, col, v, planted, la, fl)
+        fn = f"vd_ca_{family}_hub_mix.npz"
+        write(fn, values=bits(v), planted=planted, rounds=np.array(VD_ROUNDS, dtype=np.int32), last_avg=bits(la), flows=bits(fl))
+        out["ca"][family] = {"file": fn, "graph": manifest["engine_rules"]["lossy"]["file"], "counts": counts(VD_ROUNDS, la, fl)}
+
+    # ---- the lossy, pair and churn rules on the recorded masks, matchings and topologies
+    src = np.repeat(np.arange(n), np.diff(rowptr))
+    for family in VD_RULE_FAMILIES:
+        v, planted = vd_values(family, rowptr, col, churn_alive)
+        isp = np.zeros(n, dtype=bool)
+        isp[planted] = True
+
+        d = rule["lossy"]
+        stops = tuple(int(s) for s in d["stops"])
+        D = np.unpackbits(d["delivered"], axis=1)[:, :E].astype(bool)
+        res = ca_lossy_sync(rowptr, col, rev, v, D, stops, seed=1)
+        la, fl = np.stack([res[s][0] for s in stops]), np.stack([res[s][1] for s in stops])
+        odd = (bits(fl) == NEG_ZERO) | ~np.isfinite(fl)
+        assert any((odd[q] & ~D[s]).any() for q, s in enumerate(stops[:-1])), "lossy: no loss on a -0.0 or non-finite stored flow"
+        fn = f"vd_lossy_{family}_hub_mix.npz"
+        write(fn, values=bits(v), planted=planted, stops=d["stops"], last_avg=bits(la), flows=bits(fl))
+        out["rule"][f"lossy_{family}"] = {"file": fn, "rule": manifest["engine_rules"]["lossy"]["file"], "counts": counts(stops, la, fl)}
+
+        d = rule["pair"]
+        stops = tuple(int(s) for s in d["stops"])
+        res = pw_sync(rowptr, col, v, d["mate"], d["initiator"], stops, seed=2)
+        la, fl, es = (np.stack([res[s][k] for s in stops]) for k in range(3))
+        assert (d["mate"][:, planted] >= 0).any() and (d["mate"] < 0).all(axis=0).any(), "pair: no planted pair or no never-fired node"
+        fn = f"vd_pair_{family}_hub_mix.npz"
+        write(fn, values=bits(v), planted=planted, stops=d["stops"], last_avg=bits(la), flows=bits(fl), estimates=bits(es))
+        out["rule"][f"pair_{family}"] = {"file": fn, "rule": manifest["engine_rules"]["pair"]["file"], "counts": counts(stops, la, fl)}
+
+        d = rule["churn"]
+        stops = tuple(int(s) for s in d["stops"])
+        ev = [int(r) for r in d["event_rounds"]]
+        topo = {r: (d["alive"][e], d["link_up"][e]) for e, r in enumerate(ev) if r > 0}
+        res, events = ca_churn_sync(rowptr, col, v, topo, stops, seed=3)
+        for e, r in enumerate(ev[1:], 1):
+            assert np.array_equal(events[r][0], d["live"][e] != 0) and np.array_equal(events[r][1], d["fresh"][e] != 0)
+        la, fl = np.stack([res[s][0] for s in stops]), np.stack([res[s][1] for s in stops])
+        fresh = d["fresh"][1:] != 0
+        assert (fresh & (isp[src] | isp[col])).any() and (d["alive"][:, planted] == 0).any(), "churn: no FRESH slot or dead node among the planted"
+        fn = f"vd_churn_{family}_hub_mix.npz"
+        write(fn, values=bits(v), planted=planted, stops=d["stops"], last_avg=bits(la), flows=bits(fl))
+        out["rule"][f"churn_{family}"] = {"file": fn, "rule": manifest["engine_rules"]["churn"]["file"], "counts": counts(stops, la, fl)}
+
+    # ---- tick level: the actors of the asym12 and rr32_d4 fixtures with planted values
+    plant = {"asym12": {2: -0.0, 5: np.inf, 7: 5e-324, 9: np.nan, 11: -5e-324},
+             "rr32_d4": {3: -0.0, 8: np.inf, 13: 5e-324, 19: np.nan, 24: -5e-324, 29: -np.inf}}
+    for gname in ("asym12", "rr32_d4"):
+        for mode in ("ca", "pw"):
+            with open(os.path.join(HERE, manifest["tick"][f"{gname}_{mode}_rand11"])) as f:
+                actors = [tuple(a) for a in json.load(f)["actors"]]
+            names = [a[0] for a in actors]
+            aidx = {nm: i for i, nm in enumerate(names)}
+            actors = [(nm, repr(float(plant[gname][i])) if i in plant[gname] else val, neigh) for i, (nm, val, neigh) in enumerate(actors)]
+            planted = np.array(sorted(plant[gname]), dtype=np.int32)
+            res = tick_emulation(mode, actors, VD_TICKS, VD_TICK_ORDER, log_payloads=True)
+            na = len(actors)
+            decl = [[aidx[x] for x in a[2].split(",")] if a[2] else [] for a in actors]
+            keys = res["snap_keys"]
+            assert all(keys[t] == keys[-1][:len(keys[t])] for t in range(VD_TICKS))  # a dict: keys only join, at the end
+            snaps = np.zeros((VD_TICKS, na), dtype=np.float64)
+            for t in range(VD_TICKS):
+                snaps[t, keys[t]] = res["snap_vals"][t]
+            seen, dyn, dyn_pay = set(), [], []
+            for q, fl_, es_ in res["recv_payloads"]:
+                t, i, _, s = res["events"][q]
+                if s not in decl[i] and (i, s) not in seen:  # CA:94-96 / PW:94-96: the sender joins i's neighbours
+                    seen.add((i, s))
+                    dyn.append((t, i, s))
+                    dyn_pay.append((fl_, es_))
+            assert len(dyn) == res["errors_logged"]
+            if gname == "asym12":
+                assert any(s in plant[gname] and not (np.isfinite(es_) and abs(es_) >= 2.0 ** -1022) for (_, _, s), (_, es_) in zip(dyn, dyn_pay)), \
+                    "tick: no dynamic addition carries a planted value"
+            fn = f"vd_tick_{gname}_{mode}.npz"
+            write(fn, names=np.array(names), value_strs=np.array([a[1] for a in actors]), values=bits([float(a[1]) for a in actors]),
+                  planted=planted, decl_rowptr=np.cumsum([0] + [len(r) for r in decl]).astype(np.int64),
+                  decl_col=np.array([c for r in decl for c in r], dtype=np.int32),
+                  mode=np.array([mode]), order=np.array([VD_TICK_ORDER]), ticks=np.array([VD_TICKS], dtype=np.int32),
+                  key_order=np.array(keys[-1], dtype=np.int32), n_keys=np.array([len(k) for k in keys], dtype=np.int32), snaps=bits(snaps),
+                  events=np.array(res["events"], dtype=np.int32).reshape(-1, 4), fires=np.array(res["fires"], dtype=np.int32),
+                  union_rowptr=np.cumsum([0] + [len(r) for r in res["neighbors"]]).astype(np.int64),
+                  union_col=np.array([c for r in res["neighbors"] for c in r], dtype=np.int32),
+                  flows=bits([x for r in res["flows"] for x in r]), estimates=bits([x for r in res["estimates"] for x in r]),
+                  dyn=np.array(dyn, dtype=np.int32).reshape(-1, 3), dyn_payload=bits(np.array(dyn_pay, dtype=np.float64).reshape(-1, 2)),
+                  errors_logged=np.array([res["errors_logged"]], dtype=np.int32))
+            last = np.array([snaps[-1]])
+            out["tick"][f"{gname}_{mode}"] = {"file": fn, "actors": manifest["tick"][f"{gname}_{mode}_rand11"],
+                                              "counts": {str(VD_TICKS - 1): {"estimates": vd_counts(last), "flows": vd_counts([x for r in res["flows"] for x in r])}}}
+
+
 def parse_actors_xml(path):
     import xml.etree.ElementTree as ET
 
@@ -783,6 +1021,13 @@ def main():
         print("make_golden: the fixtures pin the reference under CPython < 3.12 (sum() over floats is "
               f"compensated from 3.12 on); this is {sys.version.split()[0]}: nothing written")
         return 2
+    if "--only-value-domain" in sys.argv:  # the last stage alone, on the manifest and files of the earlier ones
+        with open(os.path.join(HERE, "MANIFEST.json")) as f:
+            manifest = json.load(f)
+        value_domain_fixtures(manifest)
+        with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
+            json.dump(manifest, f, indent=1)
+        return 0
     platform_summary()
     if "--only-platform" in sys.argv:
         return 0
@@ -856,6 +1101,9 @@ def main():
 
     # ---------------- the lossy, pair and churn rules ----------------
     engine_rule_fixtures(manifest)
+
+    # ---------------- the fp64 value domain through every driver ----------------
+    value_domain_fixtures(manifest)
 
     with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1)

@@ -6,7 +6,12 @@ binade boundary, mixed-sign subnormals, overflow to +-inf and NaN) go through ev
 compared with the C oracle by bit pattern (parity_util.assert_same_bits): the signs of zeros
 and infinities count, and a NaN must sit exactly where the oracle has one.
 
-The references are computed once per family and shared by the cases; no case changes them."""
+The references are computed once per family and shared by the cases; no case changes them.
+
+These cases prove the kernels equal to the oracle. That the oracle, and so the kernels, equal the
+reference's own Peer code on such values (signed zeros, subnormals, overflow order, NaN placement)
+is pinned in test_value_domain_golden.py (oracles against tests/golden/vd_*.npz, no GPU) and
+test_value_domain_golden_gpu.py (every engine against those files directly)."""
 import functools
 
 import numpy as np
