@@ -29,165 +29,37 @@
 // (the reverse slot has its own byte, which its own row turns), so the FRESH -> UP write goes
 // with the flow write: no race, no extra pass.
 //
-// The handle scaffold is csrc/fu_handle.h; the error check over alive nodes is this file's own.
-#include "fu_handle.h"
+// This file holds the churn rule (the state byte is the slot's kind: UP gathers, DOWN is
+// skipped, FRESH is kZero and turns UP at write-out; a dead row does not fire), the topology
+// pass and the error check over alive nodes. The round itself (the kernels, the launch plan,
+// the common buffers, the front half of create) is csrc/fu_rev_round.h, shared with the lossy
+// engine; the handle scaffold under it is csrc/fu_handle.h.
+#include "fu_rev_round.h"
 
 using namespace fu;
 
 namespace {
 
-constexpr int kBlock = 256;        // threads per block (4 waves of 64)
-constexpr int kTileRows = kBlock;  // light tiles: at most one row per thread
-constexpr int kTileEdges = 2048;   // light tiles: (F, E, state) of the tile's slots in LDS (34 KB: 4 blocks per CU)
-constexpr int kHeavyDeg = 128;     // rows above this degree run one block per row
-constexpr int kChunk = 2048;       // heavy rows: (F, E) elements staged in LDS per chunk
-
 constexpr unsigned char kUp = 0, kDown = 1, kFresh = 2;
+static_assert(kUp == kGather && kDown == kSkip && kFresh == kZero, "the state byte is the slot's kind");
 
-using i64 = long long;
-
-struct RoundArgs {
-  const i64 *rowptr;
-  const int *col, *rev;
-  const unsigned char *alive;
-  unsigned char *state;
-  const double *v, *f_old, *a_old;
-  double *f_new, *a_new;
+struct churn_rule {
+  struct Args {
+    const unsigned char *alive;
+    unsigned char *state;
+  };
+  static constexpr bool kHasOwn = false, kHasSkip = true, kDeadRows = true;
+  template <int N>
+  __device__ static void classify(const Args &X, const i64 (&k)[N], unsigned char (&kind)[N]) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) kind[u] = X.state[k[u]];
+  }
+  __device__ static bool fires(const Args &X, int row) { return X.alive[row] != 0; }
+  __device__ static void wrote(const Args &X, i64 k, unsigned char kind) {
+    if (kind == kFresh) X.state[k] = kUp;
+  }
+  __device__ static void block_end(const Args &, int &) {}
 };
-
-// Light tiles: consecutive rows of degree <= kHeavyDeg, at most kTileRows rows and kTileEdges
-// slots. All threads load the tile's slots coalesced (col, rev, state) and leave the gathered
-// (F, E) in LDS; thread t then runs row t's two chains from LDS in row order and leaves the
-// new flows there; all threads write them out coalesced and turn the FRESH bytes to UP.
-__global__ __launch_bounds__(kBlock) void kc_light(RoundArgs A, const int2 *__restrict__ tiles) {
-  __shared__ double s_F[kTileEdges], s_E[kTileEdges];
-  __shared__ unsigned char s_st[kTileEdges];
-  const int tid = threadIdx.x;
-  const int2 tile = tiles[blockIdx.x];
-  const i64 e0 = A.rowptr[tile.x];
-  const int ne = (int)(A.rowptr[tile.y] - e0);  // <= kTileEdges (the host's tile plan)
-  if (ne > 0) {
-    // Branch-free: a thread's kSlots slots (indices past the tile's end clamped to its last
-    // slot, their results dropped) issue all their loads before the first use. A slot that is
-    // not UP gathers nothing: its flow load reads its own slot (index k instead of rev k, the
-    // value dropped) and its estimate load is masked off.
-    constexpr int kSlots = kTileEdges / kBlock;
-    i64 k[kSlots];
-    int c[kSlots], rv[kSlots];
-    unsigned char st[kSlots];
-    double F[kSlots], E[kSlots];
-#pragma unroll
-    for (int u = 0; u < kSlots; ++u) {
-      const int q = tid + u * kBlock;
-      k[u] = e0 + (q < ne ? q : ne - 1);
-      c[u] = A.col[k[u]];
-      rv[u] = A.rev[k[u]];
-      st[u] = A.state[k[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < kSlots; ++u) {
-      F[u] = A.f_old[st[u] == kUp ? (i64)rv[u] : k[u]];
-      E[u] = st[u] == kUp ? A.a_old[c[u]] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kSlots; ++u) {
-      const int q = tid + u * kBlock;
-      if (q < ne) {
-        s_F[q] = st[u] == kUp ? -F[u] : 0.0;
-        s_E[q] = E[u];
-        s_st[q] = st[u];
-      }
-    }
-  }
-  __syncthreads();
-  const int row = tile.x + tid;
-  if (row < tile.y) {
-    const int b = (int)(A.rowptr[row] - e0);
-    const int d = (int)(A.rowptr[row + 1] - e0) - b;
-    double S = 0.0, T = 0.0;
-    int live = 0;
-    for (int j = b; j < b + d; ++j) {
-      S = S + s_F[j];  // a DOWN slot adds +0.0 (the argument at the top of the file)
-      T = T + s_E[j];
-      live += s_st[j] != kDown;
-    }
-    // a dead row's slots are all DOWN: its flows come out as +0.0 below
-    const double a = A.alive[row] ? ((A.v[row] - S) + T) / (double)(live + 1) : A.a_old[row];
-    A.a_new[row] = a;
-    for (int j = b; j < b + d; ++j) s_F[j] = s_st[j] != kDown ? (s_F[j] + a) - s_E[j] : 0.0;
-  }
-  __syncthreads();
-  for (int q = tid; q < ne; q += kBlock) {
-    A.f_new[e0 + q] = s_F[q];
-    if (s_st[q] == kFresh) A.state[e0 + q] = kUp;
-  }
-}
-
-// Slot k's operands and state, for the heavy rows.
-__device__ inline unsigned char fetch(const RoundArgs &A, i64 k, double &F, double &E) {
-  const unsigned char st = A.state[k];
-  if (st == kUp) {
-    F = -A.f_old[A.rev[k]];
-    E = A.a_old[A.col[k]];
-  } else {
-    F = 0.0;
-    E = 0.0;
-  }
-  return st;
-}
-
-// Rows above kHeavyDeg: one block per row. All threads load a chunk of slots coalesced and
-// leave (F, E) in LDS; lane 0 of wave 0 carries S and lane 0 of wave 1 carries T through the
-// chunk in row order, from chunk to chunk, and every thread counts the live slots it loaded,
-// over all chunks. Once the block's count and a are known, a second pass fetches the operands
-// again (f_old, a_old and the state bytes are not written before it), writes the flows
-// coalesced and turns the FRESH bytes to UP.
-__global__ __launch_bounds__(kBlock) void kc_heavy(RoundArgs A, const int *__restrict__ hrows) {
-  __shared__ double s_F[kChunk], s_E[kChunk];
-  __shared__ double s_T, s_a;
-  __shared__ int s_live[kBlock / 64];
-  const int tid = threadIdx.x;
-  const int row = hrows[blockIdx.x];
-  const i64 b = A.rowptr[row];
-  const i64 d = A.rowptr[row + 1] - b;
-  double acc = 0.0;  // S in thread 0, T in thread 64
-  int live = 0;
-  for (i64 c0 = 0; c0 < d; c0 += kChunk) {
-    const int m = (int)(d - c0 < kChunk ? d - c0 : kChunk);
-#pragma unroll 4
-    for (int q = tid; q < m; q += kBlock) {
-      double F, E;
-      live += fetch(A, b + c0 + q, F, E) != kDown;
-      s_F[q] = F;
-      s_E[q] = E;
-    }
-    __syncthreads();
-    if (tid == 0)
-      for (int q = 0; q < m; ++q) acc = acc + s_F[q];
-    else if (tid == 64)
-      for (int q = 0; q < m; ++q) acc = acc + s_E[q];
-    __syncthreads();
-  }
-  for (int off = 32; off > 0; off >>= 1) live += __shfl_xor(live, off, 64);
-  if ((tid & 63) == 0) s_live[tid >> 6] = live;
-  if (tid == 64) s_T = acc;
-  __syncthreads();
-  if (tid == 0) {
-    int dl = 0;
-    for (int q = 0; q < kBlock / 64; ++q) dl += s_live[q];
-    const double a = A.alive[row] ? ((A.v[row] - acc) + s_T) / (double)(dl + 1) : A.a_old[row];
-    A.a_new[row] = a;
-    s_a = a;
-  }
-  __syncthreads();
-  const double a = s_a;
-  for (i64 q = tid; q < d; q += kBlock) {
-    double F, E;
-    const unsigned char st = fetch(A, b + q, F, E);
-    A.f_new[b + q] = st != kDown ? (F + a) - E : 0.0;
-    if (st == kFresh) A.state[b + q] = kUp;
-  }
-}
 
 // fu_churn_set_topology and fu_churn_reset: one pass over the slots, from the uploaded alive
 // and link_up and the old state byte to the new one. Slot k's row is col[rev k]. A slot that is
@@ -243,14 +115,9 @@ int check_link_up(const char *who, int64_t e, const int32_t *rev, const uint8_t 
 
 }  // namespace
 
-struct fu_churn : handle_base {
+struct fu_churn : rev_handle {
   static constexpr const char *kTag = "fu_churn";
-  int32_t n_tiles = 0, n_heavy = 0;
-  i64 *rowptr = nullptr;
-  int *col = nullptr, *rev = nullptr, *hrows = nullptr;
-  int2 *tiles = nullptr;
   unsigned char *alive = nullptr, *link_up = nullptr, *state = nullptr;
-  double *v = nullptr, *a[2] = {nullptr, nullptr}, *f[2] = {nullptr, nullptr};
   u64 *count = nullptr;
   std::vector<int32_t> h_rev;  // host copy: the symmetry check of link_up
   int64_t stats[2] = {0, 0};   // alive nodes, live slots of the current topology
@@ -264,25 +131,7 @@ static int launch_err(fu_churn *h, u64 *slot) {
   return FU_OK;
 }
 
-static int launch_round(fu_churn *h) {
-  const int64_t r = h->round;
-  RoundArgs A;
-  A.rowptr = h->rowptr;
-  A.col = h->col;
-  A.rev = h->rev;
-  A.alive = h->alive;
-  A.state = h->state;
-  A.v = h->v;
-  A.f_old = h->f[(r + 1) & 1];
-  A.a_old = h->a[(r + 1) & 1];
-  A.f_new = h->f[r & 1];
-  A.a_new = h->a[r & 1];
-  if (h->n_tiles > 0) hipLaunchKernelGGL(kc_light, dim3(h->n_tiles), dim3(kBlock), 0, h->stream, A, h->tiles);
-  if (h->n_heavy > 0) hipLaunchKernelGGL(kc_heavy, dim3(h->n_heavy), dim3(kBlock), 0, h->stream, A, h->hrows);
-  HIP_TRY(hipGetLastError());
-  h->round = r + 1;
-  return FU_OK;
-}
+static int launch_round(fu_churn *h) { return launch_rev_round<churn_rule>(h, {h->alive, h->state}); }
 
 // The state bytes from the device's alive and link_up, behind the rounds already queued;
 // complete on return, with the counts in h->stats.
@@ -304,64 +153,26 @@ extern "C" {
 
 int fu_churn_destroy(fu_churn *h) {
   if (!h) return bad_arguments<fu_churn>("destroy");
-  handle_close(h, {h->rowptr, h->col, h->rev, h->hrows, h->tiles, h->alive, h->link_up, h->state, h->v, h->a[0], h->a[1],
-                   h->f[0], h->f[1], h->count});
+  rev_close(h, {h->alive, h->link_up, h->state, h->count});
   delete h;
   return FU_OK;
 }
 
-// Every check on the arguments comes before the first HIP call, so a host without a GPU
-// reports an asymmetric graph or a bad rev as such.
 int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
                     const double *value, int32_t device, fu_churn **out) {
   FU_TRY_BEGIN
-  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_churn>("create");
-  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_churn_create: more than 2^31-1 directed edges (rev is int32)");
-  if (int rc = check_csr("fu_churn_create", n, e, rowptr, col)) return rc;
+  fu_churn *h = nullptr;
   std::vector<int32_t> built;
-  if (e > 0 && !rev) {
-    if (int rc = rev_of_csr(n, e, rowptr, col, &built)) return rc;
-    rev = built.data();
-  }
-  if (int rc = check_rev("fu_churn_create", RevCheck::kPairing, n, rowptr, col, rev)) return rc;
-  // the launch plan of fu_lossy_create: heavy rows one block each; the rows between them in
-  // tiles of at most kTileRows rows and kTileEdges slots
-  std::vector<int32_t> heavy;
-  std::vector<int2> tiles;
-  for (int32_t i = 0; i < n;) {
-    if (rowptr[i + 1] - rowptr[i] > kHeavyDeg) {
-      heavy.push_back(i++);
-      continue;
-    }
-    int32_t j = i;
-    while (j < n && j - i < kTileRows && rowptr[j + 1] - rowptr[j] <= kHeavyDeg && rowptr[j + 1] - rowptr[i] <= kTileEdges) ++j;
-    tiles.push_back(make_int2(i, j));  // j > i: a light row alone always fits
-    i = j;
-  }
-  auto *h = new fu_churn();
-  h->n_tiles = (int32_t)tiles.size();
-  h->n_heavy = (int32_t)heavy.size();
+  auto cleanup = [&](int code) { if (h) fu_churn_destroy(h); return code; };
+  int rc = rev_create(&h, out, n, e, rowptr, col, &rev, &built, value, device);
+  if (rc || (rc = dmalloc(h, &h->alive, n)) || (rc = dmalloc(h, &h->link_up, e)) || (rc = dmalloc(h, &h->state, e)) ||
+      (rc = dmalloc(h, &h->count, 2)))
+    return cleanup(rc);
   if (e > 0) h->h_rev.assign(rev, rev + e);
-  auto cleanup = [&](int code) { fu_churn_destroy(h); return code; };
-  int rc = FU_OK;
-  if ((rc = handle_open(h, device, n, e, 1))) return cleanup(rc);
-  const int64_t e1 = std::max<int64_t>(e, 1);
-  if ((rc = dmalloc(h, &h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(h, &h->col, e)) || (rc = dmalloc(h, &h->rev, e)) ||
-      (rc = dmalloc(h, &h->hrows, h->n_heavy)) || (rc = dmalloc(h, &h->tiles, h->n_tiles)) ||
-      (rc = dmalloc(h, &h->alive, n)) || (rc = dmalloc(h, &h->link_up, e)) || (rc = dmalloc(h, &h->state, e)) ||
-      (rc = dmalloc(h, &h->v, n)) || (rc = dmalloc(h, &h->a[0], n)) || (rc = dmalloc(h, &h->a[1], n)) ||
-      (rc = dmalloc(h, &h->f[0], e1)) || (rc = dmalloc(h, &h->f[1], e1)) || (rc = dmalloc(h, &h->count, 2)))
-    return cleanup(rc);
-  static_assert(sizeof(i64) == sizeof(int64_t), "rowptr is uploaded as is");
-  if ((rc = put(h, h->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(h, h->col, col, e)) || (rc = put(h, h->rev, rev, e)) ||
-      (rc = put(h, h->hrows, heavy.data(), h->n_heavy)) || (rc = put(h, h->tiles, tiles.data(), h->n_tiles)) ||
-      (rc = put(h, h->v, value, n)))
-    return cleanup(rc);
-  if ((rc = zero(h, h->a[0], n)) || (rc = zero(h, h->a[1], n)) || (rc = zero(h, h->f[0], e1)) || (rc = zero(h, h->f[1], e1)))
-    return cleanup(rc);
   // everything alive and up, every slot FRESH
-  if (hipMemset(h->alive, 1, (size_t)n) != hipSuccess || hipMemset(h->link_up, 1, (size_t)e1) != hipSuccess ||
-      hipMemset(h->state, kFresh, (size_t)e1) != hipSuccess)
+  const size_t e1 = (size_t)std::max<int64_t>(e, 1);
+  if (hipMemset(h->alive, 1, (size_t)n) != hipSuccess || hipMemset(h->link_up, 1, e1) != hipSuccess ||
+      hipMemset(h->state, kFresh, e1) != hipSuccess)
     return cleanup(fail(FU_ERR_HIP, "fu_churn_create: memset failed"));
   h->stats[0] = n;
   h->stats[1] = e;
@@ -393,10 +204,7 @@ int fu_churn_set_topology(fu_churn *h, const uint8_t *alive, const uint8_t *link
   FU_TRY_END
 }
 
-int fu_churn_set_values(fu_churn *h, const double *value) {
-  if (!h || !value) return bad_arguments<fu_churn>("set_values");
-  return upload(h, h->v, value, sizeof(double) * (size_t)h->n);
-}
+int fu_churn_set_values(fu_churn *h, const double *value) { return set_values(h, value); }
 
 // Dead nodes keep their estimate and DOWN slots their +0.0 from round to round, so the
 // buffers are zeroed here and round 0 is an ordinary round.
@@ -420,15 +228,9 @@ int fu_churn_max_err(fu_churn *h, double *out) { return max_err(h, out, /*needs_
 int fu_churn_get_round(fu_churn *h, int64_t *rounds_done) { return get_round(h, rounds_done); }
 int fu_churn_synchronize(fu_churn *h) { return synchronize(h); }
 
-int fu_churn_get_estimates(fu_churn *h, double *a_out) {
-  if (!h || !a_out) return bad_arguments<fu_churn>("get_estimates");
-  return download(h, a_out, h->a[(h->round + 1) & 1], sizeof(double) * (size_t)h->n);
-}
-
-int fu_churn_get_flows(fu_churn *h, double *f_out) {
-  if (!h || (!f_out && h->E)) return bad_arguments<fu_churn>("get_flows");
-  return download(h, f_out, h->f[(h->round + 1) & 1], sizeof(double) * (size_t)h->E);
-}
+// reset zeroes the buffers: before round 0 they download like after any round.
+int fu_churn_get_estimates(fu_churn *h, double *a_out) { return get_estimates(h, a_out, /*zero_before_round_0=*/false); }
+int fu_churn_get_flows(fu_churn *h, double *f_out) { return get_flows(h, f_out, /*zero_before_round_0=*/false); }
 
 int fu_churn_get_stats(fu_churn *h, int64_t out[2]) {
   if (!h || !out) return bad_arguments<fu_churn>("get_stats");
@@ -448,14 +250,8 @@ int fu_churn_live(int32_t n, const int64_t *rowptr, const int32_t *col, const in
   if (!rowptr || n <= 0) return bad_arguments<fu_churn>("live");
   const int64_t e = rowptr[n];
   if (e < 0 || (e > 0 && (!col || !live_out))) return bad_arguments<fu_churn>("live");
-  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_churn_live: more than 2^31-1 directed edges (rev is int32)");
-  if (int rc = check_csr("fu_churn_live", n, e, rowptr, col)) return rc;
   std::vector<int32_t> built;
-  if (e > 0 && !rev) {
-    if (int rc = rev_of_csr(n, e, rowptr, col, &built)) return rc;
-    rev = built.data();
-  }
-  if (int rc = check_rev("fu_churn_live", RevCheck::kPairing, n, rowptr, col, rev)) return rc;
+  if (int rc = pairing_rev("fu_churn_live", n, e, rowptr, col, &rev, &built)) return rc;
   if (int rc = check_link_up("fu_churn_live", e, rev, link_up)) return rc;
   for (int32_t i = 0; i < n; ++i)
     for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)

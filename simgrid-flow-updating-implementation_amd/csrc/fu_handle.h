@@ -1,6 +1,6 @@
 // The handle scaffold of the batched, lossy, pairwise and churn engines: included by
-// fu_batch.hip, fu_lossy.hip, fu_pair.hip and fu_churn.hip and by nothing else. DESIGN.md
-// §4.15-4.18.
+// fu_batch.hip, fu_pair.hip and fu_rev_round.h (the round of fu_lossy.hip and fu_churn.hip)
+// and by nothing else. DESIGN.md §4.15-4.18.
 //
 // An engine's handle derives from fu::handle_base, names itself in `kTag` ("fu_batch", ...:
 // the prefix of its entry points and of every message), and supplies
@@ -19,7 +19,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -117,6 +116,19 @@ int err_slots(H *h, int64_t count) {
   return FU_OK;
 }
 
+// The engines that gather through rev (lossy, churn, pairwise), before their first HIP call:
+// the CSR checked, *rev built into *built where the caller gave none, and checked as a pairing.
+inline int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                       const int32_t **rev, std::vector<int32_t> *built) {
+  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, who + ": more than 2^31-1 directed edges (rev is int32)");
+  if (int rc = check_csr(who.c_str(), n, e, rowptr, col)) return rc;
+  if (e > 0 && !*rev) {
+    if (int rc = rev_of_csr(n, e, rowptr, col, built)) return rc;
+    *rev = built->data();
+  }
+  return check_rev(who.c_str(), RevCheck::kPairing, n, rowptr, col, *rev);
+}
+
 // *_create, after every check on the arguments: the device, the stream, the events, and the
 // buffers every engine has. On an error the caller destroys the handle.
 template <typename H>
@@ -139,7 +151,7 @@ int handle_open(H *h, int32_t device, int32_t n, int64_t e, int32_t width) {
 }
 
 // *_destroy: waits for the stream, frees the engine's own buffers and the shared ones.
-inline void handle_close(handle_base *h, std::initializer_list<void *> own) {
+inline void handle_close(handle_base *h, const std::vector<void *> &own) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void *p : own)

@@ -338,14 +338,8 @@ int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *c
                    const double *value, int32_t device, fu_pair **out) {
   FU_TRY_BEGIN
   if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_pair>("create");
-  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, "fu_pair_create: more than 2^31-1 directed edges (rev is int32)");
-  if (int rc = check_csr("fu_pair_create", n, e, rowptr, col)) return rc;
   std::vector<int32_t> built;
-  if (e > 0 && !rev) {
-    if (int rc = rev_of_csr(n, e, rowptr, col, &built)) return rc;
-    rev = built.data();
-  }
-  if (int rc = check_rev("fu_pair_create", RevCheck::kPairing, n, rowptr, col, rev)) return rc;
+  if (int rc = pairing_rev("fu_pair_create", n, e, rowptr, col, &rev, &built)) return rc;
   int32_t heavy_rows = 0;
   for (int32_t i = 0; i < n; ++i) heavy_rows += rowptr[i + 1] - rowptr[i] > kLightDeg;
   auto *h = new fu_pair();
