@@ -1,6 +1,7 @@
 // The handle scaffold of the batched, lossy, pairwise and churn engines: included by
 // fu_batch.hip, fu_pair.hip and fu_rev_round.h (the round of fu_lossy.hip and fu_churn.hip)
-// and by nothing else. DESIGN.md §4.15-4.18.
+// and, for its stream_base part alone (a handle without targets), by fu_replay.hip. DESIGN.md
+// §4.15-4.18.
 //
 // An engine's handle derives from fu::handle_base, names itself in `kTag` ("fu_batch", ...:
 // the prefix of its entry points and of every message), and supplies
@@ -12,7 +13,7 @@
 // and the small entry points. Where the engines differ on purpose, the difference is an
 // argument (max_err's needs_a_round), not a second copy.
 //
-// Everything but handle_base has internal linkage: each engine file gets its own kernels.
+// Everything but the two base structs has internal linkage: each engine file gets its own kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,15 +36,19 @@ namespace fu {
 
 using u64 = unsigned long long;
 
-struct handle_base {
+// What every device handle has (the tick replay's, fu_replay.hip, has nothing more of the below).
+struct stream_base {
   int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+struct handle_base : stream_base {
   int32_t n = 0;
   int32_t width = 1;  // error slots per check: 1, or the batch's K
   int64_t E = 0;
   int64_t round = 0;
   bool has_target = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double *target = nullptr;  // n * width
   u64 *err = nullptr;        // errcap slots, width per check
   int64_t errcap = 0;
@@ -91,7 +96,7 @@ int bad_arguments(const char *entry) {
   return fail(FU_ERR_ARG, std::string(H::kTag) + "_" + entry + ": bad arguments");
 }
 
-inline int set_device(const handle_base *h) {
+inline int set_device(const stream_base *h) {
   HIP_TRY(hipSetDevice(h->device));
   return FU_OK;
 }
@@ -129,38 +134,46 @@ inline int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64
   return check_rev(who.c_str(), RevCheck::kPairing, n, rowptr, col, *rev);
 }
 
-// *_create, after every check on the arguments: the device, the stream, the events, and the
-// buffers every engine has. On an error the caller destroys the handle.
+// *_create, after every check on the arguments: the device, the stream and the events. On an
+// error the caller destroys the handle.
 template <typename H>
-int handle_open(H *h, int32_t device, int32_t n, int64_t e, int32_t width) {
+int stream_open(H *h, int32_t device) {
   const std::string who = std::string(H::kTag) + "_create";
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, who + ": no HIP device visible");
   if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, who + ": device out of range");
   h->device = device;
-  h->n = n;
-  h->E = e;
-  h->width = width;
   if (int rc = set_device(h)) return rc;
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
     return fail(FU_ERR_HIP, who + ": hipStreamCreate failed");
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
     return fail(FU_ERR_HIP, who + ": hipEventCreate failed");
+  return FU_OK;
+}
+// The same, and the buffers every round engine has.
+template <typename H>
+int handle_open(H *h, int32_t device, int32_t n, int64_t e, int32_t width) {
+  h->n = n;
+  h->E = e;
+  h->width = width;
+  if (int rc = stream_open(h, device)) return rc;
   if (int rc = dmalloc(h, &h->target, (int64_t)n * width)) return rc;
   return err_slots(h, width);
 }
 
-// *_destroy: waits for the stream, frees the engine's own buffers and the shared ones.
-inline void handle_close(handle_base *h, const std::vector<void *> &own) {
+// *_destroy: waits for the stream, frees the handle's buffers, the events and the stream.
+inline void stream_close(stream_base *h, const std::vector<void *> &own) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void *p : own)
     if (p) (void)hipFree(p);
-  if (h->target) (void)hipFree(h->target);
-  if (h->err) (void)hipFree(h->err);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
+}
+inline void handle_close(handle_base *h, std::vector<void *> own) {
+  own.insert(own.end(), {h->target, h->err});
+  stream_close(h, own);
 }
 
 // *_create: count elements of T to or at dst, synchronously; nothing for count == 0.
@@ -178,7 +191,7 @@ int zero(H *, T *dst, int64_t count) {
 }
 
 // A live handle: over its stream, complete on return.
-inline int upload(handle_base *h, void *dst, const void *src, size_t bytes) {
+inline int upload(stream_base *h, void *dst, const void *src, size_t bytes) {
   FU_TRY_BEGIN
   if (int rc = set_device(h)) return rc;
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
@@ -186,7 +199,7 @@ inline int upload(handle_base *h, void *dst, const void *src, size_t bytes) {
   return FU_OK;
   FU_TRY_END
 }
-inline int download(handle_base *h, void *dst, const void *src, size_t bytes) {
+inline int download(stream_base *h, void *dst, const void *src, size_t bytes) {
   FU_TRY_BEGIN
   if (bytes == 0) return FU_OK;
   if (int rc = set_device(h)) return rc;

@@ -676,7 +676,7 @@ int fu_trace_free(fu_trace *t) {
   return FU_OK;
 }
 
-// Accessors used by the device side (fu_engine.hip) without exposing the struct layout.
+// Accessors used by the device side (fu_replay.hip) without exposing the struct layout.
 const fu_trace *fu__trace_view(const fu_trace *t, int32_t *n, int32_t *ticks,
                                const int64_t **urowptr, const int64_t **tto,
                                const int32_t **tasks, int64_t *n_tasks,

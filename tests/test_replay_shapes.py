@@ -324,6 +324,20 @@ def test_persistent_blocks_option():
         rep.close()
 
 
+@gpu
+def test_device_out_of_range_then_a_good_create():
+    """device == device_count is refused by name, leaves nothing behind, and device 0 still opens."""
+    key = ("rr9", "pairwise")
+    with pytest.raises(fu.FuError) as e:
+        fu.Replay(_trace(*key), _values(key, "uniform"), device=fu.device_count())
+    assert e.value.code == -1 and "fu_replay_create: device out of range" in str(e.value)
+    rep = _open(key, "uniform", False)
+    try:
+        _run_segments(rep, key, "uniform", ((TICKS, SNAPS),), (key, "after a refused create"))
+    finally:
+        rep.close()
+
+
 # ------------------------------------------------------------------------------------
 # 7. degenerate shapes
 # ------------------------------------------------------------------------------------
