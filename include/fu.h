@@ -271,6 +271,21 @@ int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
                     const int32_t *rev, const double *value, int32_t device, fu_lossy **out);
 int fu_lossy_create_from_graph(const fu_graph *g, const double *value, int32_t device,
                                fu_lossy **out);
+/* K value columns over one graph under one loss pattern, 1 <= k <= 16 (else FU_ERR_ARG):
+ * value[n*k], node-major (value[i*k + c]). One message carries all k (flow, estimate) pairs, so
+ * the loss decision, the mask and the statistics are per slot, exactly those of a handle of one
+ * column with the same (seed, p, mask), and column c is bit-equal to a fu_lossy_create handle
+ * run on column c alone. On such a handle every entry point below works with arrays scaled as in
+ * fu_batch: set_values, set_targets and get_estimates take or return n*k doubles (x[i*k + c]),
+ * get_flows returns e*k doubles (f[slot*k + c], the caller's slot order), the error trace has
+ * (rounds / err_every) * k entries, round-major, and max_err writes out[k]. */
+int fu_lossy_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                      const int32_t *rev, int32_t k, const double *value /* n*k */, int32_t device,
+                      fu_lossy **out);
+int fu_lossy_create_from_graph_k(const fu_graph *g, int32_t k, const double *value,
+                                 int32_t device, fu_lossy **out);
+/* The handle's number of columns (1 for fu_lossy_create). */
+int fu_lossy_get_columns(fu_lossy *h, int32_t *k);
 /* Loss probability and seed of the rounds run after the call (defaults 0, 0). p outside
  * [0, 1] or NaN: FU_ERR_ARG. */
 int fu_lossy_set_loss(fu_lossy *h, double p, uint64_t seed);
@@ -281,13 +296,14 @@ int fu_lossy_set_link_mask(fu_lossy *h, const uint8_t *down);
 int fu_lossy_set_values(fu_lossy *h, const double *value);
 /* Zero the state, the round counter and the statistics. Loss, mask and values are kept. */
 int fu_lossy_reset(fu_lossy *h);
-/* As fu_batch_run with k = 1: rounds / err_every entries of max_i |a_i - target_i|. */
+/* As fu_batch_run with the handle's k (1 for fu_lossy_create): (rounds / err_every) * k entries
+ * of max_i |a[i][c] - target[i][c]|, round-major. */
 int fu_lossy_run(fu_lossy *h, int32_t rounds, int32_t err_every, double *err_trace);
 int fu_lossy_run_timed(fu_lossy *h, int32_t rounds, float *ms);
 int fu_lossy_set_targets(fu_lossy *h, const double *target);
 int fu_lossy_max_err(fu_lossy *h, double *out);
-int fu_lossy_get_estimates(fu_lossy *h, double *a_out /* n */);
-int fu_lossy_get_flows(fu_lossy *h, double *f_out /* e */);
+int fu_lossy_get_estimates(fu_lossy *h, double *a_out /* n, or n*k */);
+int fu_lossy_get_flows(fu_lossy *h, double *f_out /* e, or e*k */);
 int fu_lossy_get_round(fu_lossy *h, int64_t *rounds_done);
 /* out[0] = messages offered since the last reset (e per round >= 1), out[1] = how many of
  * them were lost (loss probability or mask). Synchronises. */
@@ -337,6 +353,19 @@ int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
                     const int32_t *rev, const double *value, int32_t device, fu_churn **out);
 int fu_churn_create_from_graph(const fu_graph *g, const double *value, int32_t device,
                                fu_churn **out);
+/* K value columns over one graph under one topology, 1 <= k <= 16 (else FU_ERR_ARG): value[n*k],
+ * node-major. Topology, slot states and statistics are per node and per slot as for one column
+ * (get_slot_state stays e bytes); a slot that goes DOWN loses all its k flow entries; column c is
+ * bit-equal to a fu_churn_create handle run on column c alone. The arrays of the entry points
+ * below scale as for fu_lossy_create_k; the error entries are per column over the alive nodes,
+ * and a NaN raises only its own column's. */
+int fu_churn_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                      const int32_t *rev, int32_t k, const double *value /* n*k */, int32_t device,
+                      fu_churn **out);
+int fu_churn_create_from_graph_k(const fu_graph *g, int32_t k, const double *value,
+                                 int32_t device, fu_churn **out);
+/* The handle's number of columns (1 for fu_churn_create). */
+int fu_churn_get_columns(fu_churn *h, int32_t *k);
 /* alive[n] and link_up[e], non-zero = on, NULL = all ones. Ordered behind the rounds already
  * queued; complete on return. */
 int fu_churn_set_topology(fu_churn *h, const uint8_t *alive, const uint8_t *link_up);
@@ -350,8 +379,8 @@ int fu_churn_run(fu_churn *h, int32_t rounds, int32_t err_every, double *err_tra
 int fu_churn_run_timed(fu_churn *h, int32_t rounds, float *ms);
 int fu_churn_set_targets(fu_churn *h, const double *target);
 int fu_churn_max_err(fu_churn *h, double *out);
-int fu_churn_get_estimates(fu_churn *h, double *a_out /* n */);
-int fu_churn_get_flows(fu_churn *h, double *f_out /* e */);
+int fu_churn_get_estimates(fu_churn *h, double *a_out /* n, or n*k */);
+int fu_churn_get_flows(fu_churn *h, double *f_out /* e, or e*k */);
 int fu_churn_get_round(fu_churn *h, int64_t *rounds_done);
 /* out[0] = alive nodes, out[1] = live directed slots, of the current topology. */
 int fu_churn_get_stats(fu_churn *h, int64_t out[2]);

@@ -63,13 +63,13 @@ struct churn_rule {
 
 // fu_churn_set_topology and fu_churn_reset: one pass over the slots, from the uploaded alive
 // and link_up and the old state byte to the new one. Slot k's row is col[rev k]. A slot that is
-// not live loses its flow entry in `f`, the buffer the next round reads. all_fresh (reset):
+// not live loses its K flow entries in `f` (f[k * K ..]), the buffer the next round reads. all_fresh (reset):
 // every live slot ends FRESH. count[0] += alive nodes, count[1] += live slots, one atomic per
 // block and counter.
 __global__ __launch_bounds__(kBlock) void kc_topology(int n, i64 E, const int *__restrict__ col, const int *__restrict__ rev,
                                                       const unsigned char *__restrict__ alive,
                                                       const unsigned char *__restrict__ link_up, unsigned char *__restrict__ state,
-                                                      double *__restrict__ f, int all_fresh, u64 *__restrict__ count) {
+                                                      double *__restrict__ f, int K, int all_fresh, u64 *__restrict__ count) {
   const i64 k = (i64)blockIdx.x * kBlock + threadIdx.x;
   int live = 0;
   if (k < E) {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void kc_topology(int n, i64 E, const int *_
       if (all_fresh || state[k] == kDown) state[k] = kFresh;
     } else {
       state[k] = kDown;
-      f[k] = 0.0;
+      for (int c = 0; c < K; ++c) f[k * K + c] = 0.0;
     }
   }
   int up = k < n && alive[k] != 0;
@@ -124,6 +124,7 @@ struct fu_churn : rev_handle {
 };
 
 static int launch_err(fu_churn *h, u64 *slot) {
+  if (h->width > 1) return launch_max_err_cols(h, h->alive, slot);
   const unsigned grid = (unsigned)std::min<int64_t>(1024, ((int64_t)h->n + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(kc_max_err, dim3(grid), dim3(kBlock), 0, h->stream, h->n, h->a[(h->round + 1) & 1], h->target, h->alive,
                      slot);  // a of the last round run
@@ -139,7 +140,7 @@ static int apply_topology(fu_churn *h, bool all_fresh) {
   const int64_t work = std::max<int64_t>(h->E, h->n);
   HIP_TRY(hipMemsetAsync(h->count, 0, 2 * sizeof(u64), h->stream));
   hipLaunchKernelGGL(kc_topology, dim3((unsigned)((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->n, (i64)h->E,
-                     h->col, h->rev, h->alive, h->link_up, h->state, h->f[(h->round + 1) & 1], all_fresh ? 1 : 0, h->count);
+                     h->col, h->rev, h->alive, h->link_up, h->state, h->f[(h->round + 1) & 1], h->width, all_fresh ? 1 : 0, h->count);
   HIP_TRY(hipGetLastError());
   u64 c[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(c, h->count, sizeof(c), hipMemcpyDeviceToHost, h->stream));
@@ -158,13 +159,14 @@ int fu_churn_destroy(fu_churn *h) {
   return FU_OK;
 }
 
-int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
-                    const double *value, int32_t device, fu_churn **out) {
+// The back half of both creates: the topology and the slot states, per node and per slot.
+static int churn_create(const char *entry, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                        int32_t k, const double *value, int32_t device, fu_churn **out) {
   FU_TRY_BEGIN
   fu_churn *h = nullptr;
   std::vector<int32_t> built;
   auto cleanup = [&](int code) { if (h) fu_churn_destroy(h); return code; };
-  int rc = rev_create(&h, out, n, e, rowptr, col, &rev, &built, value, device);
+  int rc = rev_create(&h, out, entry, n, e, rowptr, col, &rev, &built, k, value, device);
   if (rc || (rc = dmalloc(h, &h->alive, n)) || (rc = dmalloc(h, &h->link_up, e)) || (rc = dmalloc(h, &h->state, e)) ||
       (rc = dmalloc(h, &h->count, 2)))
     return cleanup(rc);
@@ -181,9 +183,29 @@ int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
   FU_TRY_END
 }
 
+int fu_churn_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                    const double *value, int32_t device, fu_churn **out) {
+  return churn_create("create", n, e, rowptr, col, rev, 1, value, device, out);
+}
+
+int fu_churn_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev, int32_t k,
+                      const double *value, int32_t device, fu_churn **out) {
+  return churn_create("create_k", n, e, rowptr, col, rev, k, value, device, out);
+}
+
 int fu_churn_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_churn **out) {
   return create_from_graph<fu_churn>(g, value, out, [&](auto... csr) { return fu_churn_create(csr..., value, device, out); });
 }
+
+int fu_churn_create_from_graph_k(const fu_graph *g, int32_t k, const double *value, int32_t device, fu_churn **out) {
+  FU_TRY_BEGIN
+  if (g && value && out && (k < 1 || k > kMaxCols))  // after the null checks, before the graph's
+    return fail(FU_ERR_ARG, "fu_churn_create_from_graph_k: k must be in 1..16, got " + std::to_string(k));
+  return create_from_graph<fu_churn>(g, value, out, [&](auto... csr) { return fu_churn_create_k(csr..., k, value, device, out); });
+  FU_TRY_END
+}
+
+int fu_churn_get_columns(fu_churn *h, int32_t *k) { return get_columns(h, k); }
 
 int fu_churn_set_topology(fu_churn *h, const uint8_t *alive, const uint8_t *link_up) {
   FU_TRY_BEGIN
@@ -213,8 +235,8 @@ int fu_churn_reset(fu_churn *h) {
   if (!h) return bad_arguments<fu_churn>("reset");
   if (int rc = set_device(h)) return rc;
   for (int q = 0; q < 2; ++q) {
-    HIP_TRY(hipMemsetAsync(h->a[q], 0, sizeof(double) * (size_t)h->n, h->stream));
-    HIP_TRY(hipMemsetAsync(h->f[q], 0, sizeof(double) * (size_t)std::max<int64_t>(h->E, 1), h->stream));
+    HIP_TRY(hipMemsetAsync(h->a[q], 0, sizeof(double) * (size_t)h->n * h->width, h->stream));
+    HIP_TRY(hipMemsetAsync(h->f[q], 0, sizeof(double) * (size_t)std::max<int64_t>(h->E * h->width, 1), h->stream));
   }
   h->round = 0;
   return apply_topology(h, /*all_fresh=*/true);

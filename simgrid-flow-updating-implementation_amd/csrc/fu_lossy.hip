@@ -72,6 +72,7 @@ struct fu_lossy : rev_handle {
 };
 
 static int launch_err(fu_lossy *h, u64 *slot) {
+  if (h->width > 1) return launch_max_err_cols(h, nullptr, slot);
   return launch_max_err<kBlock>(h, h->a[(h->round + 1) & 1], slot);  // a of the last round run
 }
 
@@ -89,12 +90,13 @@ int fu_lossy_destroy(fu_lossy *h) {
   return FU_OK;
 }
 
-int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
-                    const double *value, int32_t device, fu_lossy **out) {
+// The back half of both creates: the mask buffer and the lost-message counter, per slot.
+static int lossy_create(const char *entry, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                        int32_t k, const double *value, int32_t device, fu_lossy **out) {
   FU_TRY_BEGIN
   fu_lossy *h = nullptr;
   std::vector<int32_t> built;
-  int rc = rev_create(&h, out, n, e, rowptr, col, &rev, &built, value, device);
+  int rc = rev_create(&h, out, entry, n, e, rowptr, col, &rev, &built, k, value, device);
   if (rc || (rc = dmalloc(h, &h->down, e)) || (rc = dmalloc(h, &h->lost, 1)) || (rc = zero(h, h->lost, 1))) {
     if (h) fu_lossy_destroy(h);
     return rc;
@@ -104,9 +106,29 @@ int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *
   FU_TRY_END
 }
 
+int fu_lossy_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                    const double *value, int32_t device, fu_lossy **out) {
+  return lossy_create("create", n, e, rowptr, col, rev, 1, value, device, out);
+}
+
+int fu_lossy_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev, int32_t k,
+                      const double *value, int32_t device, fu_lossy **out) {
+  return lossy_create("create_k", n, e, rowptr, col, rev, k, value, device, out);
+}
+
 int fu_lossy_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_lossy **out) {
   return create_from_graph<fu_lossy>(g, value, out, [&](auto... csr) { return fu_lossy_create(csr..., value, device, out); });
 }
+
+int fu_lossy_create_from_graph_k(const fu_graph *g, int32_t k, const double *value, int32_t device, fu_lossy **out) {
+  FU_TRY_BEGIN
+  if (g && value && out && (k < 1 || k > kMaxCols))  // after the null checks, before the graph's
+    return fail(FU_ERR_ARG, "fu_lossy_create_from_graph_k: k must be in 1..16, got " + std::to_string(k));
+  return create_from_graph<fu_lossy>(g, value, out, [&](auto... csr) { return fu_lossy_create_k(csr..., k, value, device, out); });
+  FU_TRY_END
+}
+
+int fu_lossy_get_columns(fu_lossy *h, int32_t *k) { return get_columns(h, k); }
 
 int fu_lossy_set_loss(fu_lossy *h, double p, uint64_t seed) {
   if (!h) return bad_arguments<fu_lossy>("set_loss");

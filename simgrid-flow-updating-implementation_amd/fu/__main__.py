@@ -7,6 +7,7 @@
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 [--churn-seed 7]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 --columns 4   # or --loss
 
 Defaults mirror flowupdating-collectall.py:154,157 (./platforms/small_platform.xml,
 ./actors.xml, watcher 1000.0 / 10.0 at CA:162).
@@ -17,9 +18,28 @@ import argparse
 import sys
 import time
 
-from .engine import CollectAll, CollectAllChurn, CollectAllLossy, PairwiseSync, churn_targets
+import numpy as np
+
+from .engine import (CollectAll, CollectAllChurn, CollectAllChurnBatch, CollectAllLossy, CollectAllLossyBatch, PairwiseSync,
+                     churn_targets)
 from .graph import Graph, component_means, uniform_values
 from .sim import CollectAllPeer, Engine, run_reference_main
+
+
+def _columns(n: int, k: int):
+    """(n, k) inputs of --columns: column 0 the usual uniform values, column 1 the COUNT
+    indicator (node 0 holds 1), every further column c a uniform stream at seed c."""
+    cols = [uniform_values(n, seed=0)]
+    if k > 1:
+        one = np.zeros(n)
+        one[0] = 1.0
+        cols.append(one)
+    cols += [uniform_values(n, seed=c) for c in range(2, k)]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+def _columns_note(a) -> str:
+    return "" if a.columns is None else f" columns={a.columns}"
 
 
 def main(argv=None):
@@ -43,13 +63,24 @@ def main(argv=None):
     ap.add_argument("--churn", type=float, default=None,
                     help="bench-graph: fraction of the nodes that dies after half of the rounds (churn engine)")
     ap.add_argument("--churn-seed", type=int, default=0)
+    ap.add_argument("--columns", type=int, default=None,
+                    help="bench-graph with --loss or --churn: K value columns in one handle (1..16)")
     a = ap.parse_args(argv)
+    if a.columns is not None:
+        if a.mode != "bench-graph" or (a.loss is None and a.churn is None):
+            ap.error("--columns needs bench-graph with --loss or --churn")
+        if not 1 <= a.columns <= 16:
+            ap.error("--columns must be in 1..16")
     if a.mode == "bench-graph" and a.churn is not None:
         if a.loss is not None or a.pairs:
             ap.error("--churn is exclusive with --loss and --pairs")
         g = Graph.from_spec(a.spec, seed=a.seed)
-        v = uniform_values(g.n, seed=0)
-        eng = CollectAllChurn(g, v, device=a.device)
+        if a.columns is None:
+            v = uniform_values(g.n, seed=0)
+            eng = CollectAllChurn(g, v, device=a.device)
+        else:
+            v = _columns(g.n, a.columns)
+            eng = CollectAllChurnBatch(g, v, device=a.device)
         # node i dies iff U_i < FRACTION, U the fu_values_uniform stream at the churn seed
         alive = ~(uniform_values(g.n, seed=a.churn_seed, lo=0.0, hi=1.0) < a.churn)
         t0 = time.perf_counter()
@@ -60,7 +91,7 @@ def main(argv=None):
         wall = time.perf_counter() - t0
         print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
               f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
-              f"max_err={eng.max_err():.3e} alive={eng.stats[0]}")
+              f"max_err={np.max(eng.max_err()):.3e} alive={eng.stats[0]}" + _columns_note(a))
         return 0
     if a.mode == "bench-graph" and a.pairs:
         if a.loss is not None:
@@ -79,16 +110,19 @@ def main(argv=None):
         return 0
     if a.mode == "bench-graph" and a.loss is not None:
         g = Graph.from_spec(a.spec, seed=a.seed)
-        v = uniform_values(g.n, seed=0)
-        eng = CollectAllLossy(g, v, loss=a.loss, seed=a.loss_seed, device=a.device)
+        if a.columns is None:
+            v = uniform_values(g.n, seed=0)
+            eng = CollectAllLossy(g, v, loss=a.loss, seed=a.loss_seed, device=a.device)
+        else:
+            v = _columns(g.n, a.columns)
+            eng = CollectAllLossyBatch(g, v, loss=a.loss, seed=a.loss_seed, device=a.device)
         t0 = time.perf_counter()
         ms = eng.run_timed(a.rounds)
         wall = time.perf_counter() - t0
-        tgt, _ = component_means(g.rowptr, g.col, v)
-        eng.set_targets(tgt)
+        eng.set_targets(churn_targets(g, v))  # everything alive: component_means per column
         print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
               f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
-              f"max_err={eng.max_err():.3e} lost={eng.stats[1]}")
+              f"max_err={np.max(eng.max_err()):.3e} lost={eng.stats[1]}" + _columns_note(a))
         return 0
     if a.mode == "bench-graph":
         g = Graph.from_spec(a.spec, seed=a.seed)

@@ -92,6 +92,9 @@ _SIGS = {
     "fu_batch_destroy": ([vp], ctypes.c_int),
     "fu_lossy_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
     "fu_lossy_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_lossy_create_k": ([i32, i64, vp, vp, vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_lossy_create_from_graph_k": ([vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_lossy_get_columns": ([vp, P(i32)], ctypes.c_int),
     "fu_lossy_set_loss": ([vp, f64, u64], ctypes.c_int),
     "fu_lossy_set_link_mask": ([vp, vp], ctypes.c_int),
     "fu_lossy_set_values": ([vp, vp], ctypes.c_int),
@@ -109,6 +112,9 @@ _SIGS = {
     "fu_lossy_delivered": ([u64, i64, i64, i64, f64, vp], ctypes.c_int),
     "fu_churn_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
     "fu_churn_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_churn_create_k": ([i32, i64, vp, vp, vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_churn_create_from_graph_k": ([vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_churn_get_columns": ([vp, P(i32)], ctypes.c_int),
     "fu_churn_set_topology": ([vp, vp, vp], ctypes.c_int),
     "fu_churn_set_values": ([vp, vp], ctypes.c_int),
     "fu_churn_reset": ([vp], ctypes.c_int),

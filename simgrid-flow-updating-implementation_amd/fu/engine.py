@@ -11,6 +11,9 @@
 * `CollectAllChurn`: the same rounds while nodes and links leave and join (fu_churn_*): a slot
   state per directed slot (UP, DOWN, FRESH); a removed neighbour drops out of both sums and of
   the divisor, an added one starts from zeros; `churn_live` / `churn_targets` on the host.
+* `CollectAllLossyBatch`, `CollectAllChurnBatch`: K value columns under one loss pattern or one
+  topology (fu_lossy_create_k, fu_churn_create_k): one col, rev, kind and loss decision per
+  slot, K-wide contiguous gathers; each column bit-equal to a run of the scalar class.
 * `PairwiseSync`: synchronous pairwise rounds (fu_pair_*): a matching per round chosen on the
   device, one full pairwise exchange per matched pair; `pair_matching` restates it on the host.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
@@ -24,7 +27,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from .graph import Graph, component_means
+from .graph import Graph, components, means_of_components
 
 KERNELS = {"auto": 0, "recon": 4, "stage": 8, "pregather": 9}
 LAYOUTS = {"given": 0, "degree": 1}
@@ -348,6 +351,35 @@ class CollectAllLossy(_Handle):
         return self._stats()
 
 
+def _columns(v):
+    """The K of (n, K) values, in front of them in the *_create_k calls."""
+    return (int(v.shape[1]),)
+
+
+class CollectAllLossyBatch(CollectAllLossy):
+    """K value columns under one loss pattern (fu_lossy_create_k): `values` has shape (n, K),
+    1 <= K <= 16. One message carries all K (flow, estimate) pairs, so it is lost for every
+    column at once and `stats` counts messages; column c is a `CollectAllLossy` run of column c
+    with the same loss, seed and mask, bit for bit. estimates, targets and values are (n, K),
+    flows (E, K), the error trace (checks, K), max_err (K,).
+
+    >>> one = np.zeros(g.n); one[0] = 1.0
+    >>> eng = CollectAllLossyBatch(g, np.stack([x, one], axis=1), loss=0.1, seed=7); eng.run(400)
+    >>> avg, inv_n = eng.estimates()[5]; count, total = 1 / inv_n, avg / inv_n
+    """
+
+    _C = _c_names("fu_lossy_", create="fu_lossy_create_k", create_from_graph="fu_lossy_create_from_graph_k")
+    _NDIM = 2
+    _ROWS = "values.shape[0]"
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
+                 loss: float = 0.0, seed: int = 0, device: int = 0):
+        self._open(graph, values, rowptr, col, rev, device, extra=_columns)
+        self.K = self._cols = int(self.values.shape[1])
+        if loss != 0.0 or seed != 0:
+            self.set_loss(loss, seed)
+
+
 def _csr_of(g):
     """(rowptr, col, rev) of a Graph or of a (rowptr, col, rev) triple, rev None allowed."""
     rowptr, col, rev = g.arrays() if isinstance(g, Graph) else g
@@ -385,12 +417,19 @@ def churn_live(g, alive=None, link_up=None) -> np.ndarray:
 def churn_targets(g, values, alive=None, link_up=None) -> np.ndarray:
     """What `CollectAllChurn` converges to under (alive, link_up): per alive node the exact mean
     of the alive inputs of its component of the live graph (`component_means` of the live
-    subgraph, in the caller's numbering). A dead node's entry is its own value."""
+    subgraph, in the caller's numbering). A dead node's entry is its own value. values of shape
+    (n, K) give (n, K): the components once, the means per column."""
     rp, col, _ = _csr_of(g)
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim not in (1, 2) or v.shape[0] != len(rp) - 1:
+        raise ValueError(f"values must have shape (n,) or (n, K) with n = {len(rp) - 1}, got {v.shape}")
     live = churn_live(g, alive, link_up).astype(bool)
     src = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
     lrp = np.concatenate([[0], np.cumsum(np.bincount(src[live], minlength=len(rp) - 1))]).astype(np.int64)
-    return component_means(lrp, col[live], values)[0]
+    nc, comp = components(lrp, col[live])
+    if v.ndim == 1:
+        return means_of_components(nc, comp, v)
+    return np.stack([means_of_components(nc, comp, v[:, c]) for c in range(v.shape[1])], axis=1)
 
 
 class CollectAllChurn(_Handle):
@@ -399,7 +438,7 @@ class CollectAllChurn(_Handle):
     neighbour drops out of both sums and of the divisor and its flow entry is gone; an added one
     starts from zeros (CA:33-34, CA:94-96); a dead node keeps its last estimate. The alive nodes
     converge to the mean of the alive inputs of their component. With everything alive this is
-    `CollectAll`, bit for bit.
+    `CollectAll`, bit for bit. `CollectAllChurnBatch` runs K columns under one topology.
 
     >>> eng = CollectAllChurn(g, v); eng.run(100)
     >>> alive = np.ones(g.n, np.uint8); alive[:1000] = 0
@@ -432,6 +471,29 @@ class CollectAllChurn(_Handle):
         s = np.empty(max(self.E, 1), dtype=np.uint8)
         self._call("get_slot_state", L.ptr(s))
         return s[:self.E]
+
+
+class CollectAllChurnBatch(CollectAllChurn):
+    """K value columns under one topology (fu_churn_create_k): `values` has shape (n, K),
+    1 <= K <= 16. Topology, slot states and `stats` are per node and per slot as for one column;
+    column c is a `CollectAllChurn` run of column c under the same events, bit for bit.
+    estimates, targets and values are (n, K), flows (E, K), the error trace (checks, K),
+    max_err (K,), per column over the alive nodes.
+
+    >>> one = np.zeros(g.n); one[0] = 1.0; v = np.stack([x, one], axis=1)
+    >>> eng = CollectAllChurnBatch(g, v); eng.run(100)
+    >>> eng.set_topology(alive=alive); eng.set_targets(churn_targets(g, v, alive)); eng.run(400)
+    >>> avg, inv_n = eng.estimates()[0]; alive_count, alive_sum = 1 / inv_n, avg / inv_n
+    """
+
+    _C = _c_names("fu_churn_", set_topology="fu_churn_set_topology", get_slot_state="fu_churn_get_slot_state",
+                  create="fu_churn_create_k", create_from_graph="fu_churn_create_from_graph_k")
+    _NDIM = 2
+    _ROWS = "values.shape[0]"
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None, device: int = 0):
+        self._open(graph, values, rowptr, col, rev, device, extra=_columns)
+        self.K = self._cols = int(self.values.shape[1])
 
 
 def pair_matching(g, seed: int, r: int):

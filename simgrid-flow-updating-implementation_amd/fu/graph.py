@@ -154,20 +154,21 @@ def uniform_values(n: int, seed: int = 0, lo: float = 0.0, hi: float = 100.0) ->
     return out
 
 
-def component_means(rowptr, col, values):
-    """(per-node exact mean of its connected component, component id per node).
-
-    The convergence target of max |e_i - mean| (SURVEY.md §8(d)). Uses scipy's connected
-    components and exact summation (math.fsum) per component."""
-    import math
-
+def components(rowptr, col):
+    """(number of connected components, component id per node), by scipy."""
     from scipy.sparse import csr_matrix
     from scipy.sparse.csgraph import connected_components
 
     n = len(rowptr) - 1
     m = csr_matrix((np.ones(len(col), dtype=np.int8), np.asarray(col), np.asarray(rowptr)),
                    shape=(n, n))
-    nc, comp = connected_components(m, directed=False)
+    return connected_components(m, directed=False)
+
+
+def means_of_components(nc, comp, values):
+    """Per node the exact mean (math.fsum) of `values` over its component (`components`)."""
+    import math
+
     order = np.argsort(comp, kind="stable")
     bounds = np.searchsorted(comp[order], np.arange(nc + 1))
     vals = np.asarray(values, dtype=np.float64)[order]
@@ -182,4 +183,13 @@ def component_means(rowptr, col, values):
     for k in np.nonzero(size > 2)[0]:
         seg = vals[bounds[k]:bounds[k + 1]]
         means[k] = math.fsum(seg.tolist()) / len(seg)
-    return means[comp], comp
+    return means[comp]
+
+
+def component_means(rowptr, col, values):
+    """(per-node exact mean of its connected component, component id per node).
+
+    The convergence target of max |e_i - mean| (SURVEY.md §8(d)). Uses scipy's connected
+    components and exact summation (math.fsum) per component."""
+    nc, comp = components(rowptr, col)
+    return means_of_components(nc, comp, values), comp
