@@ -124,9 +124,9 @@ def oracle_lossy(rowptr, col, rev, values, rounds, delivered, snaps=()):
 # ------------------------------------------------------------------------------------
 # (b) the rule on Python floats
 # ------------------------------------------------------------------------------------
-def lossy_python(rowptr, col, rev, values, rounds, delivered):
+def lossy_python(rowptr, col, rev, values, rounds, delivered, keep=None):
     """(a, f) after `rounds` rounds. values: one array, or a callable r -> array (the inputs of
-    round r)."""
+    round r). keep: a list that gets (a, f) after every round, in order."""
     rp, col, rev = [int(x) for x in rowptr], [int(x) for x in col], [int(x) for x in rev]
     n, E = len(rp) - 1, rp[-1]
     a_old, f_old = [0.0] * n, [0.0] * E
@@ -153,6 +153,8 @@ def lossy_python(rowptr, col, rev, values, rounds, delivered):
             for q, k in enumerate(range(rp[i], rp[i + 1])):
                 f_new[k] = (Fs[q] + a) - Es[q]
         a_old, f_old = a_new, f_new
+        if keep is not None:
+            keep.append((np.array(a_old, dtype=np.float64), np.array(f_old, dtype=np.float64)))
     return np.array(a_old, dtype=np.float64), np.array(f_old, dtype=np.float64)
 
 

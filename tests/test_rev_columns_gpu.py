@@ -3,7 +3,12 @@ csrc/fu_rev_round.h k_light_cols and k_heavy_cols): every column of a K-column r
 of a reference run of that column alone, and what belongs to a message (the loss decision, the
 statistics, the slot states) is that of one column. The references never run the engine:
 churn_cases.churn_python, lossy_cases.oracle_lossy / lossy_python once per column, the recordings
-of the reference's Peer code (rule_cases), coracle.ca_sync on the live subgraph."""
+of the reference's Peer code (rule_cases), coracle.ca_sync on the live subgraph.
+
+Nearly every value here is fu.uniform_values: one sign, one decade, no zero, nothing non-finite.
+Signed zeros, subnormals, overflow, infinities and NaN as columns, against the reference's
+value-domain recordings, are in test_rev_columns_value_domain_gpu.py (inputs and Python references:
+test_rev_columns_value_domain.py, rev_columns_vd_cases.py)."""
 import numpy as np
 import pytest
 

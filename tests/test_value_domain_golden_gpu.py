@@ -5,6 +5,11 @@ must give those bits (parity_util.assert_same_bits: signs of zeros and infinitie
 exactly where the reference has NaN). test_value_domain_golden.py holds the oracles to the same
 files on the CPU, so a disagreement here is the kernel's alone.
 
+Here: CollectAll in 12 configurations, CollectAllBatch, the scalar CollectAllLossy, PairwiseSync,
+the scalar CollectAllChurn, Replay and the drop-in Engine. The K-column handles CollectAllLossyBatch
+and CollectAllChurnBatch (k_light_cols, k_heavy_cols, k_max_err_cols) are held to the same files
+in test_rev_columns_value_domain_gpu.py.
+
 Everything runs on hub_mix (2400 nodes: rows of 2101 and 130 slots, light rows, 142 isolated rows)
 for at most 40 rounds, or on 12 and 32 actors for 120 ticks."""
 import functools
