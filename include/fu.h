@@ -421,6 +421,25 @@ int fu_churn_live(int32_t n, const int64_t *rowptr, const int32_t *col, const in
  * antisymmetric on the pair, and in exact arithmetic both ends then hold (x_i + x_j) / 2: the
  * mass is conserved and the run is gossip averaging over the matching. Rows of different
  * pairs are disjoint, so a round updates the state in place.
+ *
+ * Message loss (fu_pair_set_loss, fu_pair_set_link_mask; off by default). The matching does not
+ * look at the loss or the mask: a peer cannot know that its message will be lost, and an
+ * initiator that proposes over a dead link fires into it. With ks = rowptr[i] + s and
+ * kt = rowptr[j] + t, a pair has two messages: m1 goes i -> j and is received on slot kt, m2
+ * goes j -> i and is received on slot ks. A message is lost by the slot that would receive it:
+ * the message received on slot k in round r is lost iff down[k] != 0 or
+ * u01(splitmix64_at(splitmix64_at(~loss_seed, r), k)) < p, u01(x) = (x >> 11) * 2^-53. The
+ * complement keeps the loss stream apart from the matching's when both seeds are one number.
+ * Round 0 is an ordinary round (fu_lossy's round 0 delivers nothing; this one can). A pure
+ * function of (loss_seed, r, k, p): fu_pair_lost restates it on the host. The outcomes:
+ *   m1 lost:       step 1 alone: f[ks] = F1, c[ks] = a_i, last[i] = a_i. Node j does nothing: its
+ *                  row is not read or written, it does not count as having fired, no m2 exists.
+ *   m2 lost:       steps 1 and 2; node i keeps what it fired, f[ks] = F1, c[ks] = a_i.
+ *   both arrive:   steps 1 to 3, the lossless exchange bit for bit.
+ * Each is the reference's avg_and_send / on_receive with one message not handed over. After a
+ * lost answer the two ends of the link hold flows that do not negate each other; the next
+ * message delivered over it, in either direction, restores that (PW:98-99). With p = 0 and no
+ * mask the handle launches the lossless kernels; with p = 1 every initiator fires alone.
  * Arguments are checked before any HIP call, also on a host without a GPU.
  * ==================================================================================== */
 typedef struct fu_pair fu_pair;
@@ -433,13 +452,20 @@ int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t de
                               fu_pair **out);
 /* Seed of the matchings of the rounds run after the call (default 0). */
 int fu_pair_set_seed(fu_pair *h, uint64_t seed);
+/* Loss probability and seed of the rounds run after the call (defaults 0, 0). p outside [0, 1]
+ * or NaN: FU_ERR_ARG. */
+int fu_pair_set_loss(fu_pair *h, double p, uint64_t seed);
+/* down[e]: a non-zero byte loses every message received on slot k in the rounds run after the
+ * call. NULL clears the mask. */
+int fu_pair_set_link_mask(fu_pair *h, const uint8_t *down);
 /* "match": how the device finds the matching, 0 = proposers push one 64-bit atomicMin per valid
  * proposal (default), 1 = every listener hashes its own row. Same matching, same bits; the
  * switch exists for the A/B of tools/bench_pair.py. Unknown key or value: FU_ERR_ARG. */
 int fu_pair_set_option(fu_pair *h, const char *key, int64_t value);
 /* The inputs change (value[n]); flows, caches, last averages and the round counter are kept. */
 int fu_pair_set_values(fu_pair *h, const double *value);
-/* Zero the state, the round counter and the statistics. Seed and values are kept. */
+/* Zero the state, the round counter and the statistics (the loss counters too). The seeds, the
+ * loss, the mask and the values are kept. */
 int fu_pair_reset(fu_pair *h);
 /* Run `rounds` rounds. If err_every > 0 (targets required), err_trace receives, after every
  * err_every-th round, max_i |last_i - target_i| (rounds / err_every entries; the maximum is
@@ -460,12 +486,19 @@ int fu_pair_get_round(fu_pair *h, int64_t *rounds_done);
 /* out[0] = pairs exchanged since the last reset, out[1] = nodes that have never fired since
  * then. Synchronises. */
 int fu_pair_get_stats(fu_pair *h, int64_t out[2]);
+/* out[0] = first messages lost, out[1] = answers lost, out[2] = complete exchanges, since the
+ * last reset; their sum is out[0] of fu_pair_get_stats, the matched pairs. Synchronises. */
+int fu_pair_get_loss_stats(fu_pair *h, int64_t out[3]);
 int fu_pair_synchronize(fu_pair *h);
 int fu_pair_destroy(fu_pair *h);
 /* Host only, no GPU: the matching of round `round` under `seed`. mate[i] = i's partner or -1,
  * initiator[i] = 1 for the proposer of a pair, else 0. */
 int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed,
                      int64_t round, int32_t *mate /* n */, uint8_t *initiator /* n */);
+/* Host only, no GPU: out[q] = 1 if the message received on slot first + q in round `round` is
+ * lost under (p, seed), no mask. */
+int fu_pair_lost(uint64_t seed, int64_t round, int64_t first, int64_t count, double p,
+                 uint8_t *out);
 
 /* ======================================================================================
  * Tick-level replay (pairwise mode, and faithful collect-all on small platforms).

@@ -18,6 +18,24 @@
 // What a pair leaves behind: f[s] = -F2, f[t] = F2, c[s] = c[t] = a_j, last[i] = a_i,
 // last[j] = a_j. Rows of different pairs are disjoint, so the update is in place.
 //
+// Under loss the matching stays what it is; the message received on slot k in
+// round r is lost iff down[k] != 0 or u01(splitmix_at(splitmix_at(~loss_seed, r), k)) < p: the
+// receiver's slot decides, as in fu_lossy.hip. With ks = rowptr[i] + s and kt = rowptr[j] + t,
+// m1 (i -> j) is received on kt and m2 (j -> i) on ks. The three outcomes of a pair:
+//   m1 lost:   step 1 alone. f[ks] = F1, c[ks] = a_i, last[i] = a_i, fired[i] = 1; row j is
+//              neither read nor written, fired[j] and last[j] stay, no m2 exists.
+//   m2 lost:   steps 1 and 2. f[kt] = F2, c[kt] = a_j, last[j] = a_j, fired[j] = 1, and node i
+//              keeps what it fired: f[ks] = F1, c[ks] = a_i.
+//   delivered: steps 1 to 3, the lossless exchange bit for bit.
+// Each is the reference's avg_and_send / on_receive with one message not handed over; the next
+// message delivered over the link, in either direction, makes f antisymmetric on it again
+// (PW:98-99). No new race: the matching does not look at the loss, so the rows of different
+// pairs are still disjoint, every outcome writes only into rows i and j of its own pair (fewer
+// slots than the full exchange, never others), `down` is read-only in a round, and the
+// counters are atomics. So the update stays in place.
+// The lossy forms of kp_exchange and kp_heavy are launched only when p > 0 or a mask is set;
+// the lossless handle runs the instantiation it always ran.
+//
 // A round is kp_propose (one 64-bit atomicMin per valid proposal into the listener's word) or
 // kp_scan (every listener hashes its own row; no atomics), then kp_exchange (a block compacts
 // its matched listeners, 8 lanes per pair load both flow rows into LDS, one lane carries the
@@ -38,6 +56,12 @@ constexpr int kGroups = kBlock / kGroup;    // pairs a block works on at once
 constexpr int kLightDeg = 64;               // a pair with a row above this degree goes to kp_heavy
 constexpr int kChunk = 1024;                // kp_heavy: flows staged in LDS per chunk
 constexpr int kHeavyBlocks = 1024;          // kp_heavy: at most this many blocks share the round's heavy pairs
+
+// The lost-message counters: kLostLines pairs (first messages lost, answers lost), a 128-byte
+// line each; block b adds into pair b % kLostLines and fu_pair_get_loss_stats sums them. With
+// one pair for all blocks the two more atomics per block on the line of the pair counter doubled
+// the round.
+constexpr int kLostLines = 64, kLostStride = 16;
 
 constexpr u64 kNone = ~0ull;  // a listener's word without a proposal (no key is all-ones: i < 2^31)
 
@@ -73,12 +97,33 @@ struct RoundArgs {
   unsigned *n_heavy;
   int32_t heavy_cap;
   uint64_t key;          // round_key(seed, r)
+  static constexpr bool kLossy = false;
 };
 
 // One fire and the answer to it, from the two sums: what the pair writes back.
 struct Exchange {
   double a_i, a_j, F2;
 };
+
+// The arguments of the lossy forms of the exchange kernels: kp_exchange<LossArgs> and
+// kp_heavy<LossArgs>. The lossless handle runs kp_exchange<RoundArgs> and kp_heavy<RoundArgs>.
+struct LossArgs : RoundArgs {
+  const unsigned char *down;  // per slot: non-zero loses every message received on it; may be null
+  u64 *lost;                  // the handle's counter pairs: [q * kLostStride] first messages lost, [.. + 1] answers lost
+  uint64_t lkey;              // loss_key(loss_seed, r)
+  double p;
+  static constexpr bool kLossy = true;
+};
+
+// The key of round r's loss decisions (the complement keeps the stream apart from the
+// matching's when both seeds are the same number), and the decision for the message received
+// on slot k: the kernels and fu_pair_lost share both. The compare is fp64 on both sides.
+FU_HD inline uint64_t loss_key(uint64_t seed, uint64_t r) { return splitmix_at(~seed, r); }
+FU_HD inline bool slot_lost(uint64_t key, uint64_t k, double p) { return u01(splitmix_at(key, k)) < p; }
+__device__ inline bool message_lost(const LossArgs &X, int64_t k) {
+  return (X.down != nullptr && X.down[k] != 0) || (X.p > 0.0 && slot_lost(X.lkey, (uint64_t)k, X.p));
+}
+
 __device__ inline double fire_avg(double c, double v, double S) { return (c + (v - S)) / 2.0; }
 
 // ---- matching, form A: proposers push -----------------------------------------------------
@@ -112,7 +157,14 @@ __global__ __launch_bounds__(kBlock) void kp_scan(RoundArgs A) {
 // pairs (ballot, listener order) and works on kGroups of them at a time: the 8 lanes of a
 // group load the pair's two flow rows coalesced into the group's LDS rows, then lane 0 runs
 // both chains from LDS in row order.
-__global__ __launch_bounds__(kBlock) void kp_exchange(RoundArgs A) {
+//
+// Args::kLossy: all 8 lanes of a group read rev[ks] (one address: a broadcast) and with it hold both
+// decisions of the pair, so a group whose m1 is lost never loads row j. The barriers of the q0
+// loop stay outside every per-pair branch. The lost messages are counted per thread and added
+// with one atomic per block and counter.
+template <class Args>
+__global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
+  constexpr bool kLossy = Args::kLossy;
   __shared__ int2 s_pair[kBlock];
   __shared__ int s_cnt[kBlock / 64];
   __shared__ double s_f[kGroups][2 * kLightDeg];
@@ -135,9 +187,10 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(RoundArgs A) {
   if (matched) s_pair[base + __popcll(bal & ((1ull << lane) - 1))] = make_int2((int)(uint32_t)word, (int)node);
   __syncthreads();
   const int g = tid / kGroup, l = tid % kGroup;
+  int n_lost1 = 0, n_lost2 = 0;  // kLossy: this thread's pairs (lane 0 of a group counts)
   for (int q0 = 0; q0 < np; q0 += kGroups) {  // np is the same in every thread: the barriers are uniform
     const int q = q0 + g;
-    bool light = false;
+    bool light = false, lost1 = false, lost2 = false;
     int i = 0, j = 0, di = 0, dj = 0, t = 0;
     int64_t bi = 0, bj = 0, ks = 0;
     double cs = 0.0, vi = 0.0, vj = 0.0;
@@ -157,12 +210,26 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(RoundArgs A) {
         light = true;
         ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
         for (int d = l; d < di; d += kGroup) s_f[g][d] = A.f[bi + d];
-        for (int d = l; d < dj; d += kGroup) s_f[g][kLightDeg + d] = A.f[bj + d];
-        if (l == 0) {
-          t = (int)(A.rev[ks] - bj);
-          cs = A.c[ks];
-          vi = A.v[i];
-          vj = A.v[j];
+        if constexpr (kLossy) {
+          const int64_t kt = A.rev[ks];  // in row j: fu_pair_create checked rev as a pairing
+          t = (int)(kt - bj);
+          lost1 = message_lost(A, kt);
+          lost2 = message_lost(A, ks);
+          if (!lost1)
+            for (int d = l; d < dj; d += kGroup) s_f[g][kLightDeg + d] = A.f[bj + d];
+          if (l == 0) {
+            cs = A.c[ks];
+            vi = A.v[i];
+            if (!lost1) vj = A.v[j];
+          }
+        } else {
+          for (int d = l; d < dj; d += kGroup) s_f[g][kLightDeg + d] = A.f[bj + d];
+          if (l == 0) {
+            t = (int)(A.rev[ks] - bj);
+            cs = A.c[ks];
+            vi = A.v[i];
+            vj = A.v[j];
+          }
         }
       }
     }
@@ -173,39 +240,70 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(RoundArgs A) {
       for (int d = 0; d < di; ++d) S = S + fi[d];
       const double a_i = fire_avg(cs, vi, S);
       const double F1 = (fi[ks - bi] + a_i) - cs;
-      S = 0.0;
-      for (int d = 0; d < dj; ++d) S = S + (d == t ? -F1 : fj[d]);
-      const double a_j = fire_avg(a_i, vj, S);
-      const double F2 = (-F1 + a_j) - a_i;
-      A.f[ks] = -F2;
-      A.c[ks] = a_j;
-      A.f[bj + t] = F2;
-      A.c[bj + t] = a_j;
-      A.last[i] = a_i;
-      A.last[j] = a_j;
-      A.fired[i] = 1;
-      A.fired[j] = 1;
+      if (kLossy && lost1) {  // i fired into a message nobody received
+        A.f[ks] = F1;
+        A.c[ks] = a_i;
+        A.last[i] = a_i;
+        A.fired[i] = 1;
+        n_lost1 += 1;
+      } else {
+        S = 0.0;
+        for (int d = 0; d < dj; ++d) S = S + (d == t ? -F1 : fj[d]);
+        const double a_j = fire_avg(a_i, vj, S);
+        const double F2 = (-F1 + a_j) - a_i;
+        if (kLossy && lost2) {  // j answered, i never heard it
+          A.f[ks] = F1;
+          A.c[ks] = a_i;
+          n_lost2 += 1;
+        } else {
+          A.f[ks] = -F2;
+          A.c[ks] = a_j;
+        }
+        A.f[bj + t] = F2;
+        A.c[bj + t] = a_j;
+        A.last[i] = a_i;
+        A.last[j] = a_j;
+        A.fired[i] = 1;
+        A.fired[j] = 1;
+      }
     }
     __syncthreads();
   }
   if (tid == 0 && np > 0) atomicAdd(A.pairs, (u64)np);
+  if constexpr (kLossy) {
+    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
+    block_count_to<kBlock>(n_lost1, mine);
+    __syncthreads();  // block_count_to's LDS words are read by thread 0 until here
+    block_count_to<kBlock>(n_lost2, mine + 1);
+  }
 }
 
 // Pairs with a row above kLightDeg: one block per pair, at most kHeavyBlocks blocks sharing the
 // list. All threads load a chunk of a row coalesced into LDS; thread 0 carries the sum through
 // the chunk in row order, from chunk to chunk, first over row i and then, with -F1 in slot t's
 // place, over row j.
-__global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
+//
+// Args::kLossy: every thread holds kt and the loss key, so every thread of the block takes the same
+// decision on m1 and the chunk loop of row j, which has barriers, is skipped by all or by none.
+template <class Args>
+__global__ __launch_bounds__(kBlock) void kp_heavy(Args A) {
+  constexpr bool kLossy = Args::kLossy;
   __shared__ double s_f[kChunk];
   const int tid = threadIdx.x;
   const unsigned listed = *A.n_heavy;
   const unsigned cnt = (int64_t)listed < A.heavy_cap ? listed : (unsigned)A.heavy_cap;
+  unsigned n_lost1 = 0, n_lost2 = 0;  // kLossy: thread 0 counts this block's pairs
   for (unsigned q = blockIdx.x; q < cnt; q += gridDim.x) {
     const int i = A.heavy[q].x, j = A.heavy[q].y;
     const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
     const int64_t bj = A.rowptr[j], dj = A.rowptr[j + 1] - bj;
     const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
     const int64_t kt = A.rev[ks];
+    bool lost1 = false, lost2 = false;
+    if constexpr (kLossy) {
+      lost1 = message_lost(A, kt);
+      lost2 = message_lost(A, ks);
+    }
     double S = 0.0;
     for (int64_t c0 = 0; c0 < di; c0 += kChunk) {
       const int m = (int)(di - c0 < kChunk ? di - c0 : kChunk);
@@ -221,6 +319,16 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
       a_i = fire_avg(cs, A.v[i], S);
       F1 = (A.f[ks] + a_i) - cs;
     }
+    if (kLossy && lost1) {  // the same in every thread of the block
+      if (tid == 0) {
+        A.f[ks] = F1;
+        A.c[ks] = a_i;
+        A.last[i] = a_i;
+        A.fired[i] = 1;
+        n_lost1 += 1;
+      }
+      continue;
+    }
     S = 0.0;
     for (int64_t c0 = 0; c0 < dj; c0 += kChunk) {
       const int m = (int)(dj - c0 < kChunk ? dj - c0 : kChunk);
@@ -235,8 +343,14 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
     if (tid == 0) {
       const double a_j = fire_avg(a_i, A.v[j], S);
       const double F2 = (-F1 + a_j) - a_i;
-      A.f[ks] = -F2;
-      A.c[ks] = a_j;
+      if (kLossy && lost2) {
+        A.f[ks] = F1;
+        A.c[ks] = a_i;
+        n_lost2 += 1;
+      } else {
+        A.f[ks] = -F2;
+        A.c[ks] = a_j;
+      }
       A.f[kt] = F2;
       A.c[kt] = a_j;
       A.last[i] = a_i;
@@ -244,6 +358,11 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(RoundArgs A) {
       A.fired[i] = 1;
       A.fired[j] = 1;
     }
+  }
+  if constexpr (kLossy) {
+    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
+    if (tid == 0 && n_lost1) atomicAdd(mine, (u64)n_lost1);
+    if (tid == 0 && n_lost2) atomicAdd(mine + 1, (u64)n_lost2);
   }
 }
 
@@ -269,8 +388,14 @@ struct fu_pair : handle_base {
   unsigned char *fired = nullptr;
   int2 *heavy = nullptr;
   unsigned *n_heavy = nullptr;
-  u64 *stat = nullptr;  // [0] pairs exchanged, [1] scratch of kp_count_unfired
+  u64 *stat = nullptr;  // [0] matched pairs, [1] scratch of kp_count_unfired, from [2] on the kLostLines lost-message counter pairs
+  double p = 0.0;       // loss probability and seed of the rounds launched from now on
+  uint64_t loss_seed = 0;
+  bool has_mask = false;
+  unsigned char *down = nullptr;  // E bytes, allocated when a mask is first set
 };
+
+constexpr int kStats = 2 + kLostLines * kLostStride;
 
 static unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
 
@@ -299,9 +424,20 @@ static int launch_round(fu_pair *h) {
       hipLaunchKernelGGL(kp_propose, grid, block, 0, h->stream, A);
     else
       hipLaunchKernelGGL(kp_scan, grid, block, 0, h->stream, A);
-    hipLaunchKernelGGL(kp_exchange, grid, block, 0, h->stream, A);
-    if (h->n_heavy_rows > 0)
-      hipLaunchKernelGGL(kp_heavy, dim3(std::min(h->n_heavy_rows, kHeavyBlocks)), block, 0, h->stream, A);
+    const dim3 heavy_grid(std::min(h->n_heavy_rows, kHeavyBlocks));
+    if (h->p > 0.0 || h->has_mask) {
+      LossArgs X;
+      static_cast<RoundArgs &>(X) = A;
+      X.down = h->has_mask ? h->down : nullptr;
+      X.lost = h->stat + 2;
+      X.lkey = loss_key(h->loss_seed, (uint64_t)h->round);
+      X.p = h->p;
+      hipLaunchKernelGGL(kp_exchange<LossArgs>, grid, block, 0, h->stream, X);
+      if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy<LossArgs>, heavy_grid, block, 0, h->stream, X);
+    } else {  // no loss, no mask: the lossless kernels as they always ran
+      hipLaunchKernelGGL(kp_exchange<RoundArgs>, grid, block, 0, h->stream, A);
+      if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy<RoundArgs>, heavy_grid, block, 0, h->stream, A);
+    }
     HIP_TRY(hipGetLastError());
   }
   h->round += 1;
@@ -316,7 +452,7 @@ static int zero_state(fu_pair *h) {
   HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n, h->stream));
   HIP_TRY(hipMemsetAsync(h->fired, 0, n, h->stream));
   HIP_TRY(hipMemsetAsync(h->word, 0xFF, sizeof(u64) * n, h->stream));
-  HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * 2, h->stream));
+  HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * kStats, h->stream));
   HIP_TRY(hipMemsetAsync(h->n_heavy, 0, sizeof(unsigned), h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->round = 0;
@@ -327,7 +463,7 @@ extern "C" {
 
 int fu_pair_destroy(fu_pair *h) {
   if (!h) return bad_arguments<fu_pair>("destroy");
-  handle_close(h, {h->rowptr, h->col, h->rev, h->v, h->f, h->c, h->last, h->word, h->fired, h->heavy, h->n_heavy, h->stat});
+  handle_close(h, {h->rowptr, h->col, h->rev, h->v, h->f, h->c, h->last, h->word, h->fired, h->heavy, h->n_heavy, h->stat, h->down});
   delete h;
   return FU_OK;
 }
@@ -350,7 +486,7 @@ int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *c
   if ((rc = dmalloc(h, &h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(h, &h->col, e)) || (rc = dmalloc(h, &h->rev, e)) ||
       (rc = dmalloc(h, &h->v, n)) || (rc = dmalloc(h, &h->f, e)) || (rc = dmalloc(h, &h->c, e)) ||
       (rc = dmalloc(h, &h->last, n)) || (rc = dmalloc(h, &h->word, n)) || (rc = dmalloc(h, &h->fired, n)) ||
-      (rc = dmalloc(h, &h->heavy, heavy_rows)) || (rc = dmalloc(h, &h->n_heavy, 1)) || (rc = dmalloc(h, &h->stat, 2)))
+      (rc = dmalloc(h, &h->heavy, heavy_rows)) || (rc = dmalloc(h, &h->n_heavy, 1)) || (rc = dmalloc(h, &h->stat, kStats)))
     return cleanup(rc);
   if ((rc = put(h, h->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(h, h->col, col, e)) || (rc = put(h, h->rev, rev, e)) ||
       (rc = put(h, h->v, value, n)) || (rc = zero_state(h)))
@@ -368,6 +504,31 @@ int fu_pair_set_seed(fu_pair *h, uint64_t seed) {
   if (!h) return bad_arguments<fu_pair>("set_seed");
   h->seed = seed;  // a kernel argument of the rounds launched from now on
   return FU_OK;
+}
+
+int fu_pair_set_loss(fu_pair *h, double p, uint64_t seed) {
+  if (!h) return bad_arguments<fu_pair>("set_loss");
+  if (!(p >= 0.0 && p <= 1.0)) return fail(FU_ERR_ARG, "fu_pair_set_loss: p must be in [0, 1]");
+  h->p = p;  // kernel arguments of the rounds launched from now on
+  h->loss_seed = seed;
+  return FU_OK;
+}
+
+int fu_pair_set_link_mask(fu_pair *h, const uint8_t *down) {
+  FU_TRY_BEGIN
+  if (!h) return bad_arguments<fu_pair>("set_link_mask");
+  if (!down || h->E == 0) {
+    h->has_mask = false;  // rounds already queued keep their own argument copy; the buffer stays
+    return FU_OK;
+  }
+  if (int rc = set_device(h)) return rc;
+  if (!h->down)
+    if (int rc = dmalloc(h, &h->down, h->E)) return rc;
+  // over the handle's stream: the rounds queued before the call read the old bytes first
+  if (int rc = upload(h, h->down, down, (size_t)h->E)) return rc;
+  h->has_mask = true;
+  return FU_OK;
+  FU_TRY_END
 }
 
 int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
@@ -428,6 +589,34 @@ int fu_pair_get_stats(fu_pair *h, int64_t out[2]) {
   out[1] = (int64_t)s[1];
   return FU_OK;
   FU_TRY_END
+}
+
+// complete = matched pairs minus the two kinds of loss: the lossless kernels count pairs only.
+int fu_pair_get_loss_stats(fu_pair *h, int64_t out[3]) {
+  FU_TRY_BEGIN
+  if (!h) return fail(FU_ERR_ARG, "fu_pair_get_loss_stats: the handle is NULL");
+  if (!out) return fail(FU_ERR_ARG, "fu_pair_get_loss_stats: out is NULL (three int64 are written)");
+  std::vector<u64> s((size_t)kStats);
+  if (int rc = download(h, s.data(), h->stat, sizeof(u64) * s.size())) return rc;
+  u64 lost1 = 0, lost2 = 0;
+  for (int q = 0; q < kLostLines; ++q) {
+    lost1 += s[2 + q * kLostStride];
+    lost2 += s[3 + q * kLostStride];
+  }
+  out[0] = (int64_t)lost1;
+  out[1] = (int64_t)lost2;
+  out[2] = (int64_t)(s[0] - lost1 - lost2);
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_lost(uint64_t seed, int64_t round, int64_t first, int64_t count, double p, uint8_t *out) {
+  if (round < 0 || first < 0 || count < 0 || (count > 0 && !out) || !(p >= 0.0 && p <= 1.0))
+    return fail(FU_ERR_ARG, "fu_pair_lost: bad arguments");
+  if (first > INT64_MAX - count) return fail(FU_ERR_ARG, "fu_pair_lost: first + count is past 2^63 - 1");
+  const uint64_t key = loss_key(seed, (uint64_t)round);
+  for (int64_t q = 0; q < count; ++q) out[q] = p > 0.0 && slot_lost(key, (uint64_t)(first + q), p) ? 1 : 0;
+  return FU_OK;
 }
 
 int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed, int64_t round, int32_t *mate,

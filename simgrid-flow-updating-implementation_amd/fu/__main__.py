@@ -6,6 +6,7 @@
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 [--churn-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 --columns 4   # or --loss
 
@@ -56,7 +57,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--kernel", default="auto")
-    ap.add_argument("--loss", type=float, default=None, help="bench-graph: message loss probability (lossy engine)")
+    ap.add_argument("--loss", type=float, default=None, help="bench-graph: message loss probability (lossy engine; with --pairs the pair engine)")
     ap.add_argument("--loss-seed", type=int, default=0)
     ap.add_argument("--pairs", action="store_true", help="bench-graph: synchronous pairwise rounds (pair engine)")
     ap.add_argument("--pair-seed", type=int, default=0)
@@ -94,11 +95,13 @@ def main(argv=None):
               f"max_err={np.max(eng.max_err()):.3e} alive={eng.stats[0]}" + _columns_note(a))
         return 0
     if a.mode == "bench-graph" and a.pairs:
-        if a.loss is not None:
-            ap.error("--pairs and --loss are exclusive")
+        if a.columns is not None:
+            ap.error("--columns needs --loss or --churn without --pairs")
         g = Graph.from_spec(a.spec, seed=a.seed)
         v = uniform_values(g.n, seed=0)
         eng = PairwiseSync(g, v, seed=a.pair_seed, device=a.device)
+        if a.loss is not None:
+            eng.set_loss(a.loss, a.loss_seed)
         t0 = time.perf_counter()
         ms = eng.run_timed(a.rounds)
         wall = time.perf_counter() - t0
@@ -106,7 +109,8 @@ def main(argv=None):
         eng.set_targets(tgt)
         print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
               f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
-              f"max_err={eng.max_err():.3e} pairs={eng.stats[0]}")
+              f"max_err={eng.max_err():.3e} pairs={eng.stats[0]}"
+              + ("" if a.loss is None else f" lost={sum(eng.loss_stats[:2])}"))
         return 0
     if a.mode == "bench-graph" and a.loss is not None:
         g = Graph.from_spec(a.spec, seed=a.seed)

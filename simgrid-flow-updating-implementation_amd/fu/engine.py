@@ -510,6 +510,15 @@ def pair_matching(g, seed: int, r: int):
     return mate[:n], init[:n]
 
 
+def pair_lost(seed: int, round: int, first: int, count: int, p: float) -> np.ndarray:
+    """uint8[count]: 1 where the message received on slot first + q in round `round` is lost
+    under (p, seed) and no mask, the decision of `PairwiseSync` restated on the host
+    (fu_pair_lost; no GPU)."""
+    out = np.empty(max(int(count), 1), dtype=np.uint8)
+    L.call("fu_pair_lost", int(seed), int(round), int(first), int(count), float(p), L.ptr(out))
+    return out[:int(count)]
+
+
 class PairwiseSync(_Handle):
     """Synchronous pairwise rounds (fu_pair_*): every round a matching of the graph is chosen on
     the device (a pure function of seed, round and graph) and each matched pair runs one full
@@ -519,19 +528,45 @@ class PairwiseSync(_Handle):
 
     >>> eng = PairwiseSync(g, uniform_values(g.n, seed=0), seed=7)
     >>> eng.run(1000); est = eng.estimates(); pairs, never_fired = eng.stats
+
+    With `loss` > 0 or a `link_mask`, each of a pair's two messages can be lost, decided by the
+    slot that would receive it (a pure function of loss_seed, round and slot; `pair_lost` restates
+    it). A lost first message leaves the initiator's fire standing and the listener untouched; a
+    lost answer leaves both fires standing; the next message delivered over the link heals it.
+
+    >>> eng = PairwiseSync(g, uniform_values(g.n, seed=0), seed=7, loss=0.1, loss_seed=3)
+    >>> eng.run(2000); first_lost, answers_lost, complete = eng.loss_stats
     """
 
     _C = _c_names("fu_pair_")
 
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
-                 seed: int = 0, device: int = 0):
+                 seed: int = 0, loss: float = 0.0, loss_seed: int = 0, link_mask=None, device: int = 0):
         self._open(graph, values, rowptr, col, rev, device)
         if seed != 0:
             self.set_seed(seed)
+        try:
+            if loss != 0.0 or loss_seed != 0:
+                self.set_loss(loss, loss_seed)
+            if link_mask is not None:
+                self.set_link_mask(link_mask)
+        except Exception:
+            self.close()  # a bad loss or mask: the handle just opened does not wait for the collector
+            raise
 
     def set_seed(self, seed: int):
         """Seed of the matchings of the rounds run from now on."""
         L.call("fu_pair_set_seed", self._h, int(seed))
+
+    def set_loss(self, p: float, seed: int = 0):
+        """Loss probability in [0, 1] and loss seed of the rounds run from now on."""
+        L.call("fu_pair_set_loss", self._h, float(p), int(seed))
+
+    def set_link_mask(self, down):
+        """down: E entries, non-zero = every message received on that slot is lost in the rounds
+        run from now on; None clears the mask."""
+        d = _mask(down, self.E, "link_mask")
+        L.call("fu_pair_set_link_mask", self._h, L.ptr(d) if d is not None and self.E else None)
 
     def set_option(self, key: str, value: int):
         """"match": 0 = proposers push (atomicMin, default), 1 = listeners scan their rows."""
@@ -553,8 +588,16 @@ class PairwiseSync(_Handle):
 
     @property
     def stats(self) -> tuple:
-        """(pairs exchanged, nodes that have never fired) since the last reset; synchronises."""
+        """(pairs matched, nodes that have never fired) since the last reset; synchronises."""
         return self._stats()
+
+    @property
+    def loss_stats(self) -> tuple:
+        """(first messages lost, answers lost, complete exchanges) since the last reset: the
+        three outcomes of the matched pairs; synchronises."""
+        s = np.zeros(3, dtype=np.int64)
+        L.call("fu_pair_get_loss_stats", self._h, L.ptr(s))
+        return int(s[0]), int(s[1]), int(s[2])
 
 
 class Trace:

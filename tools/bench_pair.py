@@ -17,7 +17,15 @@
    flows, two caches, two last averages; the matching's own traffic is not in it), roofline =
    bytes / 8 TB/s / time, and the box's copy rate.
 
-    python tools/bench_pair.py [--rounds 200] [--n 1000000] [--reps 7] [--skip-replay]
+3. With --loss P [P ...]: in place of 2, the same two graphs and windows under message loss.
+   One handle per p (p = 0, the lossless kernels, first), all on the "atomic_min" matching; the
+   handles alternate within each repetition. One JSON line per graph and p with us_per_round,
+   the outcomes per round (first messages lost, answers lost, complete) and the byte model
+     bytes = sum over pairs of 8 (deg_i + deg_j) + 116, or 8 deg_i + 76 where m1 is lost
+   (a lost m1 skips row j, v_j and c[t] and three of the six stores; a lost m2 moves the same
+   bytes as a complete exchange; the mask-free decision reads nothing).
+
+    python tools/bench_pair.py [--rounds 200] [--n 1000000] [--reps 7] [--skip-replay] [--loss 0.1 0.3]
 """
 import argparse
 import ctypes
@@ -181,18 +189,79 @@ def big(name, g, rounds, reps, copy_gbs):
                               "pair_updates_per_s": round(2 * ppr / (t * 1e-6), 1), "copy_GBs": copy_gbs}), flush=True)
 
 
+def model_bytes_under_loss(g, seed, loss_seed, p):
+    """The byte model averaged over the pairs of rounds 1-4: 8 deg_i + 76 where m1 is lost (the
+    host's fu_pair_lost on the listener's slot), 8 (deg_i + deg_j) + 116 otherwise."""
+    deg = np.diff(g.rowptr)
+    src = np.repeat(np.arange(g.n, dtype=np.int64), deg)
+    tot = cnt = 0
+    for r in range(1, 5):
+        i, s, j, t = round_pairs(g, src, seed, r)
+        lost1 = fu.pair_lost(loss_seed, r, 0, g.E, p)[g.rowptr[j] + t] != 0
+        tot += int(np.sum(np.where(lost1, 8 * deg[i] + 76, 8 * (deg[i] + deg[j]) + 116)))
+        cnt += len(i)
+    return tot / cnt
+
+
+def big_lossy(name, g, rounds, reps, copy_gbs, losses):
+    """us per round at p = 0 (the lossless kernels) and at every p of `losses`, the handles
+    alternating within each repetition."""
+    v = fu.uniform_values(g.n, seed=0)
+    ps = [0.0] + [p for p in losses if p > 0.0]
+    engs = [fu.PairwiseSync(g, v, seed=SEED, loss=p, loss_seed=SEED) for p in ps]
+    try:
+        for eng in engs:
+            eng.run(rounds)  # warm
+        t = [[] for _ in engs]
+        for _ in range(reps):
+            for q, eng in enumerate(engs):
+                eng.reset()
+                eng.run(1)
+                eng.synchronize()
+                t[q].append(eng.run_timed(rounds - 1) * 1e3 / (rounds - 1))
+        for q, (eng, p) in enumerate(zip(engs, ps)):
+            per_round = lambda x: round(x / (rounds - 1), 1)  # noqa: E731
+            eng.reset()
+            eng.run(1)
+            eng.synchronize()
+            p0, l0 = eng.stats[0], eng.loss_stats
+            eng.run(rounds - 1)
+            ppr = (eng.stats[0] - p0) / (rounds - 1)
+            out = [per_round(a - b) for a, b in zip(eng.loss_stats, l0)]
+            per_pair = model_bytes_under_loss(g, SEED, SEED, p)
+            us = statistics.median(t[q])
+            print(json.dumps({"graph": name, "n": g.n, "E": g.E, "loss": p, "kernels": "lossy" if p > 0 else "lossless",
+                              "rounds_timed": [1, rounds - 1], "reps": reps, "us_per_round": round(us, 2),
+                              "us_per_round_min": round(min(t[q]), 2), "us_per_round_max": round(max(t[q]), 2),
+                              "pairs_per_round": round(ppr, 1), "first_lost_per_round": out[0],
+                              "answers_lost_per_round": out[1], "complete_per_round": out[2],
+                              "model_bytes_per_pair": round(per_pair, 1), "model_bytes_per_round": int(ppr * per_pair),
+                              "roofline": round(ppr * per_pair / PEAK / (us * 1e-6), 5), "copy_GBs": copy_gbs}), flush=True)
+    finally:
+        for eng in engs:
+            eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--skip-replay", action="store_true")
+    ap.add_argument("--loss", type=float, nargs="+", default=None, metavar="P",
+                    help="time the big graphs at p = 0 and at every P, in place of the A/B of the matching")
     a = ap.parse_args()
     if a.rounds < 2:
         ap.error("--rounds must be at least 2 (round 0 is not timed)")
     if not a.skip_replay:
         against_replay(a.rounds)
     copy_gbs = round(fu.copy_bandwidth(0), 1)
+    if a.loss is not None:
+        if not all(0.0 <= p <= 1.0 for p in a.loss):
+            ap.error("--loss takes probabilities in [0, 1]")
+        big_lossy(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs, a.loss)
+        big_lossy(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs, a.loss)
+        return
     big(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs)
     big(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs)
 
