@@ -39,6 +39,10 @@ through the three rule drivers on the recorded masks, matchings and topologies, 
 through `tick_emulation` on the asym12 and rr32_d4 actors. Every float in those files is stored as
 its bit pattern. `--only-value-domain` runs that stage alone on the files of the earlier ones.
 
+`row_order_fixtures` adds two collect-all recordings with shuffled rows (a hub-heavy R-MAT and a
+star), from an rng of its own; `--only-row-order` runs it alone and leaves every other file as
+it is.
+
 The reference adds with the builtin `sum` (CA:106, PW:103). From CPython 3.12 on that sum is
 compensated and no longer the left-to-right chain, so the script writes nothing there.
 
@@ -981,6 +985,44 @@ def value_domain_fixtures(manifest):
                                               "counts": {str(VD_TICKS - 1): {"estimates": vd_counts(last), "flows": vd_counts([x for r in res["flows"] for x in r])}}}
 
 
+# ----------------------------------------------------------------------------------------
+# Rows in no ascending order through the reference's Peers (ca_sync_unsorted_*.npz)
+# ----------------------------------------------------------------------------------------
+ROW_ORDER_SEED = 20261020
+ROW_ORDER_ROUNDS = [0, 1, 2, 4, 9, 29]  # six stops: the R-MAT file stays below ca_sync_rmat9_ef8.npz's size
+
+
+def row_order_fixtures(manifest):
+    """Two more collect-all recordings whose rows are shuffled (csr_from_pairs(...,
+    shuffle_rows=True)), so that the Peers' neighbour dicts, and with them the sums of CA:106 and
+    CA:110, run in an order that is not ascending on rows of up to 257 neighbours: the graph of
+    ca_sync_rmat9_ef8.npz (read back from that file) and a star with a centre of 257 leaves. The
+    stage has an rng of its own and writes only its own two files and their manifest entries;
+    `--only-row-order` runs it alone. The names sort after every earlier ca_sync name: the tests
+    parametrised over the sorted manifest carry a fixture's position in their ids, and the earlier
+    fixtures keep theirs."""
+    rng = np.random.default_rng(ROW_ORDER_SEED)
+    with np.load(os.path.join(HERE, "ca_sync_rmat9_ef8.npz")) as d:
+        rp, c = d["rowptr"].astype(np.int64), d["col"].astype(np.int64)
+    src = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    graphs = {"unsorted_rmat9_ef8": (len(rp) - 1, [(int(u), int(v)) for u, v in zip(src, c) if u < v]),
+              "unsorted_star_257": (258, [(0, i) for i in range(1, 258)])}
+    for name, (gn, pairs) in graphs.items():
+        rowptr, col = csr_from_pairs(gn, pairs, rng, shuffle_rows=True)
+        deg = np.diff(rowptr)
+        assert any(list(col[rowptr[i]:rowptr[i + 1]]) != sorted(col[rowptr[i]:rowptr[i + 1]])
+                   for i in np.flatnonzero(deg == deg.max()))
+        vals = values_for(gn, rng)
+        res = ca_sync(rowptr, col, vals, ROW_ORDER_ROUNDS, seed=int(rng.integers(1 << 31)))
+        fn = f"ca_sync_{name}.npz"
+        save_npz(os.path.join(HERE, fn), rowptr=rowptr, col=col, values=vals,
+                 rounds=np.array(ROW_ORDER_ROUNDS, dtype=np.int32),
+                 last_avg=np.stack([res[r][0] for r in ROW_ORDER_ROUNDS]),
+                 flows=np.stack([res[r][1] for r in ROW_ORDER_ROUNDS]))
+        manifest["ca_sync"][name] = {"file": fn, "n": int(gn), "E": int(len(col)), "max_deg": int(deg.max())}
+        print("ca_sync", name, gn, len(col))
+
+
 def parse_actors_xml(path):
     import xml.etree.ElementTree as ET
 
@@ -1021,10 +1063,13 @@ def main():
         print("make_golden: the fixtures pin the reference under CPython < 3.12 (sum() over floats is "
               f"compensated from 3.12 on); this is {sys.version.split()[0]}: nothing written")
         return 2
-    if "--only-value-domain" in sys.argv:  # the last stage alone, on the manifest and files of the earlier ones
+    only = [(flag, stage) for flag, stage in (("--only-value-domain", value_domain_fixtures),
+                                              ("--only-row-order", row_order_fixtures)) if flag in sys.argv]
+    if only:  # one of the last stages alone, on the manifest and files of the earlier ones
         with open(os.path.join(HERE, "MANIFEST.json")) as f:
             manifest = json.load(f)
-        value_domain_fixtures(manifest)
+        for _, stage in only:
+            stage(manifest)
         with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
             json.dump(manifest, f, indent=1)
         return 0
@@ -1104,6 +1149,9 @@ def main():
 
     # ---------------- the fp64 value domain through every driver ----------------
     value_domain_fixtures(manifest)
+
+    # ---------------- shuffled rows through the collect-all driver ----------------
+    row_order_fixtures(manifest)
 
     with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1)

@@ -45,7 +45,8 @@ def test_ca_sync_fixture_bitwise(name, meta, kernel):
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
-@pytest.mark.parametrize("name", ["rmat9_ef8", "star_257", "star_1500", "er300_m450"])
+@pytest.mark.parametrize("name", ["rmat9_ef8", "star_257", "star_1500", "er300_m450", "unsorted_rmat9_ef8",
+                                  "unsorted_star_257"])
 def test_ca_sync_fixture_heavy_path(name, kernel):
     """hub_threshold=3 sends most nodes down the heavy (block-per-node) path."""
     meta = dict(ca_sync_fixtures())[name]
