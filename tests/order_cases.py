@@ -5,7 +5,9 @@ fu_graph_from_edges return ascending rows, so on the graphs the suite already tr
 that sums in ascending id order (slice order, bucket order, chunk order) cannot be told from
 one that sums in row order. `reorder_rows` takes such a graph and permutes each row; the CPU
 conditions on these inputs are in test_order_case_inputs.py, the GPU runs in
-test_row_order_gpu.py. Numpy and the host graph code only: nothing here touches a GPU.
+test_row_order_gpu.py (uniform values) and test_row_order_values_gpu.py (the value families of
+parity_util.FAMILIES, FAMILY_TRIPLES below). Numpy and the host graph code only: nothing here
+touches a GPU.
 
 The case graphs are the ones the other modules build, reordered; their sizes and degrees are
 unchanged (rowptr is the same array)."""
@@ -19,7 +21,8 @@ from churn_cases import chunk_edge_graph
 from lossy_cases import tile_limit_graph
 from pair_cases import class_graph as pair_class_graph
 from pair_cases import dense66
-from parity_util import _batch_boundary_graph, _class_edge_graph
+from parity_util import (FAMILIES, FINITE_EXTRAS, NONFINITE_EXTRAS, PACK_STOPS, _batch_boundary_graph,
+                         _class_edge_graph)
 
 HOWS = ("random", "descending", "rotated", "zigzag")
 
@@ -165,6 +168,29 @@ GRAPHS = {
 REORDER_SEED = 1
 VALUE_SEED = {**{name: 3 for name in GRAPHS}, "batch_boundary": 4, "rmat_large": 5, "tile_limit": 6, "pack_er": 4}
 
+# The seeds of the value families, keyed (case, family), fixed the same way: seed 3 first, then
+# 4, 5, ... up to 12, the first at which the family's conditions of test_order_case_inputs.py
+# hold for every order of GPU_HOWS. Seed 3 holds but for:
+#   wide  batch_boundary 5: at 3 the centres of degree 13 (random) and 17 (rotated), at 4 those of
+#         degree 4, 8, 12 and 13 (rotated) keep the ascending order's estimate at every stop;
+#         pair_class 4: at 3 the centre of degree 7 keeps its estimate under "descending".
+#   subn  c16 4 and pack_er 4: at 3 no named row reaches -0.0.
+#   huge  rmat_small 5: at 3 and 4 its one named row (221 slots) ends in the ascending order's
+#         bits and class; c16 4: at 3 no named row differs under "rotated"; dense66 11: the first
+#         seed at which one of its two named rows changes class (zigzag); cut_slivers 7: likewise
+#         (3 to 6: no first row of a rank changes class).
+#   sym   pack_er 6: at 3 the plan's rule wavers between 16 and 8 bits from round 292 to 328, at 4
+#         and 5 it stays at 16 bits to round 328 (the mean is near zero, where the keys are sparse),
+#         so the last stop of parity_util.PACK_STOPS would not find the 8-bit table.
+# HUGE_BITWISE_ONLY: no seed from 3 to 12 makes a named row of these cases change class (their
+# named rows have 8 to 22 slots and stay finite or meet the same infinity in either order);
+# they run `huge` under the bitwise condition and the whole-graph class condition only.
+VALUE_SEED.update({(name, family): 3 for name in GRAPHS for family in FAMILIES})
+VALUE_SEED.update({("batch_boundary", "wide"): 5, ("pair_class", "wide"): 4, ("c16", "subn"): 4, ("pack_er", "subn"): 4,
+                   ("rmat_small", "huge"): 5, ("c16", "huge"): 4, ("dense66", "huge"): 11, ("cut_slivers", "huge"): 7,
+                   ("pack_er", "sym"): 6})
+HUGE_BITWISE_ONLY = ("c16", "pack_er")
+
 # The rounds in total at which the GPU tests read estimates and flows back.
 STOPS = {
     "class_edge": (1, 3, 8, 17),
@@ -197,6 +223,18 @@ GPU_HOWS = {
     "pack_er": ("random",),
 }
 
+# The value families of parity_util.FAMILIES that the GPU tests run on reordered rows, per case,
+# beside the uniform values above: the one table that test_order_case_inputs.py (the CPU
+# conditions) and test_row_order_values_gpu.py (the runs) both parametrize from.
+ORDER_FAMILIES = ("wide", "huge", "subn")
+PACK_FAMILIES = ("neg", "sym", "binade")  # the families whose table packs down to 8 bits
+GPU_FAMILIES = {name: ORDER_FAMILIES + (PACK_FAMILIES if name == "pack_er" else ()) for name in GRAPHS}
+FAMILY_TRIPLES = [(name, how, family) for name in GRAPHS for how in GPU_HOWS[name] for family in GPU_FAMILIES[name]]
+
+# `huge` stops early: once NaN has spread over a component every order agrees (NaN against NaN
+# is no difference), so a late stop detects nothing; one later stop stays, the case's last.
+STOPS_BY_FAMILY = {"huge": {name: tuple(sorted({1, 2, 3, STOPS[name][-1]})) for name in GRAPHS}}
+
 
 @functools.lru_cache(maxsize=None)
 def base_graph(name):
@@ -216,23 +254,35 @@ def graph(name, how):
 
 
 @functools.lru_cache(maxsize=None)
-def values(name):
-    v = fu.uniform_values(base_graph(name).n, seed=VALUE_SEED[name])
+def values(name, family="uniform"):
+    """The case's values: fu.uniform_values, or a family of parity_util.FAMILIES, at the seed
+    VALUE_SEED fixes for (case, family)."""
+    n = base_graph(name).n
+    if family == "uniform":
+        v = fu.uniform_values(n, seed=VALUE_SEED[name])
+    else:
+        v = FAMILIES[family](n, seed=VALUE_SEED[name, family])
     v.setflags(write=False)
     return v
 
 
+def stops(name, family="uniform"):
+    """The rounds in total at which the GPU tests of (case, family) read back."""
+    return STOPS_BY_FAMILY.get(family, STOPS)[name]
+
+
 @functools.lru_cache(maxsize=None)
-def reference(name, how, stops=None):
+def reference(name, how, stops_=None, family="uniform"):
     """{stop: (a, f)} of coracle.ca_sync on the reordered graph, computed once per case and
-    shared (read-only) by the tests. how = None: the ascending graph."""
+    family and shared (read-only) by the tests. how = None: the ascending graph."""
     g = base_graph(name) if how is None else graph(name, how)
+    v = values(name, family)
     out, done, a, f = {}, 0, None, None
-    for stop in stops or STOPS[name]:
+    for stop in stops_ or stops(name, family):
         if a is None:
-            a, f = coracle.ca_sync(*g.arrays(), values(name), stop, nthreads=8)
+            a, f = coracle.ca_sync(*g.arrays(), v, stop, nthreads=8)
         else:
-            coracle.ca_rounds(*g.arrays(), values(name), stop - done, a, f, nthreads=8)
+            coracle.ca_rounds(*g.arrays(), v, stop - done, a, f, nthreads=8)
         done = stop
         out[stop] = (a.copy(), f.copy())
         for x in out[stop]:
@@ -282,20 +332,61 @@ def named_rows(name):
     return rows
 
 
-def differing_rows(name, how):
+def _differs(x, y):
+    """assert_same_bits' rule, element by element: NaN against NaN is no difference."""
+    xn, yn = np.isnan(x), np.isnan(y)
+    bits = lambda z: np.ascontiguousarray(z).view(np.uint64)  # noqa: E731
+    return (xn != yn) | (~(xn | yn) & (bits(x) != bits(y)))
+
+
+def differing_rows(name, how, family="uniform"):
     """(estimate differs, some flow differs): bool per row, true where the C oracle on the
-    reordered graph and on the ascending one differ in bits, slot for slot, at one of the
-    case's stops at least (the GPU tests compare at every stop)."""
+    reordered graph and on the ascending one differ, slot for slot, at one of the stops of
+    (case, family) at least (the GPU tests compare at every stop). A difference is judged as
+    parity_util.assert_same_bits judges it."""
     g, base = graph(name, how), base_graph(name)
-    got, asc = reference(name, how), reference(name, None)
+    got, asc = reference(name, how, None, family), reference(name, None, None, family)
     m = slot_map(g, base)
     src = np.repeat(np.arange(g.n), base.degrees)
-    bits = lambda x: np.ascontiguousarray(x).view(np.uint64)  # noqa: E731
     da, df = np.zeros(g.n, dtype=bool), np.zeros(g.n, dtype=bool)
-    for stop in STOPS[name]:
-        da |= bits(got[stop][0]) != bits(asc[stop][0])
-        df[src[bits(got[stop][1]) != bits(asc[stop][1])[m]]] = True
+    for stop in stops(name, family):
+        da |= _differs(got[stop][0], asc[stop][0])
+        df[src[_differs(got[stop][1], asc[stop][1][m])]] = True
     return da, df
+
+
+def value_class(x):
+    """0 finite, 1 +inf, 2 -inf, 3 NaN, per element."""
+    x = np.asarray(x)
+    return np.where(np.isnan(x), 3, np.where(np.isposinf(x), 1, np.where(np.isneginf(x), 2, 0)))
+
+
+def class_changing_rows(name, how, family="huge"):
+    """bool per row: the row's estimate, or one of its flows, is of another class (finite, +inf,
+    -inf, NaN) on the reordered graph than on the ascending one at one of the stops."""
+    g, base = graph(name, how), base_graph(name)
+    got, asc = reference(name, how, None, family), reference(name, None, None, family)
+    m = slot_map(g, base)
+    src = np.repeat(np.arange(g.n), base.degrees)
+    out = np.zeros(g.n, dtype=bool)
+    for stop in stops(name, family):
+        out |= value_class(got[stop][0]) != value_class(asc[stop][0])
+        out[src[value_class(got[stop][1]) != value_class(asc[stop][1][m])]] = True
+    return out
+
+
+def neg_zero_rows(name, how, family="subn"):
+    """bool per row: the reordered oracle holds -0.0 in the row's estimate or in one of its
+    flows at one of the stops."""
+    g = graph(name, how)
+    got = reference(name, how, None, family)
+    src = np.repeat(np.arange(g.n), g.degrees)
+    nz = lambda x: np.ascontiguousarray(x).view(np.uint64) == np.uint64(1 << 63)  # noqa: E731
+    out = np.zeros(g.n, dtype=bool)
+    for stop in stops(name, family):
+        out |= nz(got[stop][0])
+        out[src[nz(got[stop][1])]] = True
+    return out
 
 
 EXEMPT_DEGREES = (0, 1, 2)  # one order only (0, 1), or a sum of two terms, which commutes (2)
@@ -323,3 +414,86 @@ def cut_options(name):
     from dist_cases import RMAT_HUB, RMAT_MEGA
 
     return {"hub_threshold": RMAT_HUB, "mega_hub": RMAT_MEGA} if name == "cut_rmat" else {}
+
+
+# ------------------------------------------------------------------------------------
+# pack_er with the packing families: small components beside it, behind the escape code
+# ------------------------------------------------------------------------------------
+def with_components(g, v, extras):
+    """g with its rows as they are and v, plus one small component per entry of `extras` (a
+    pair, or three nodes closed to a triangle, as test_value_domain._giant_with_extras adds
+    them) carrying that entry's values; the new rows follow g's."""
+    rp, col, val, k = [np.asarray(g.rowptr, dtype=np.int64)], [np.asarray(g.col, dtype=np.int32)], [np.asarray(v)], g.n
+    end = int(g.rowptr[-1])
+    for comp in extras:
+        m = len(comp)
+        assert m in (2, 3)
+        rows = [[k + 1], [k]] if m == 2 else [[k + 2, k + 1], [k, k + 2], [k + 1, k]]
+        for row in rows:
+            col.append(np.array(row, dtype=np.int32))
+            end += len(row)
+            rp.append(np.array([end], dtype=np.int64))
+        val.append(np.array(comp, dtype=np.float64))
+        k += m
+    return fu.Graph.from_csr(np.concatenate(rp), np.concatenate(col)), np.concatenate(val)
+
+
+@functools.lru_cache(maxsize=None)
+def pack_graph(family, extras="nonfinite"):
+    """(g, v): pack_er with shuffled rows and the family's values, and beside it the components
+    of parity_util.NONFINITE_EXTRAS (or FINITE_EXTRAS): +-inf, NaN, -0.0, +-5e-324 and
+    1.7e308, which never enter the packed window."""
+    g, v = with_components(graph("pack_er", "random"), values("pack_er", family),
+                           {"nonfinite": NONFINITE_EXTRAS, "finite": FINITE_EXTRAS, "signed_zero": SIGNED_ZERO_EXTRAS}[extras])
+    v.setflags(write=False)
+    return g, v
+
+
+# A pair and a triangle of subnormals whose estimates keep returning to -0.0 (with period 2 and
+# 3) while a flow and the node's own estimate sum to -0.0: there (F + a) - E is -0.0 for E = +0.0
+# and +0.0 for E = -0.0, so the sign of a gathered zero shows in the flows for as long as the
+# rounds go on (test_signed_zero_extras_show_the_sign_of_a_gathered_zero). Elsewhere T = 0.0 + E..
+# absorbs it, which is why the components of test_value_domain.py do not show it.
+SIGNED_ZERO_EXTRAS = [(-5e-324, -5e-324), (5e-324, -5e-324, -1.5e-323)]
+
+
+def pack_stops(family, extras="nonfinite"):
+    """The case's stops, then parity_util.PACK_STOPS: the table at 32, 16 and 8 bits; with
+    the signed-zero components one and two rounds more, for their periods."""
+    last = PACK_STOPS[family][-1]
+    return STOPS["pack_er"] + PACK_STOPS[family] + ((last + 1, last + 2) if extras == "signed_zero" else ())
+
+
+PACK_SETTLED = 8  # rounds before a stop over which the plan's rule gives the stop's width already
+
+
+@functools.lru_cache(maxsize=None)
+def pack_reference(family, extras="nonfinite"):
+    """{rounds: (a, f)} of the oracle on pack_graph at pack_stops and PACK_SETTLED rounds
+    before each packing stop, computed once and shared read-only."""
+    g, v = pack_graph(family, extras)
+    at = sorted(set(pack_stops(family, extras)) | {r - PACK_SETTLED for r in PACK_STOPS[family]})
+    out, done, a, f = {}, 0, None, None
+    for r in at:
+        if a is None:
+            a, f = coracle.ca_sync(*g.arrays(), v, r, nthreads=8)
+        else:
+            coracle.ca_rounds(*g.arrays(), v, r - done, a, f, nthreads=8)
+        done = r
+        out[r] = (a.copy(), f.copy())
+        for x in out[r]:
+            x.setflags(write=False)
+    return out
+
+
+STRADDLE_STEPS = (8, 16, 24, 32)
+
+
+@functools.lru_cache(maxsize=None)
+def straddle_values():
+    """Mixed-sign subnormals on pack_er at the seed of
+    test_value_domain.test_packing_window_straddles_signed_zero: the first plan packs to 8 bits
+    with both zeros inside the window."""
+    v = FAMILIES["subn"](base_graph("pack_er").n, seed=1)
+    v.setflags(write=False)
+    return v

@@ -119,6 +119,164 @@ def test_results_depend_on_the_row_order(name, how):
         assert same == (stop == 1), (name, how, stop)
 
 
+def _named(name):
+    deg = oc.base_graph(name).degrees
+    return [i for i in oc.named_rows(name) if int(deg[i]) not in oc.EXEMPT_DEGREES]
+
+
+@pytest.mark.parametrize("name,how,family", oc.FAMILY_TRIPLES)
+def test_family_results_depend_on_the_row_order(name, how, family):
+    """The same condition for the value families of order_cases.GPU_FAMILIES, for exactly the
+    (case, order, family) triples test_row_order_values_gpu.py runs, at the family's stops and
+    judged as assert_same_bits judges (NaN against NaN is no difference).
+
+    wide, neg, sym, binade: every named row of three or more slots differs in its estimate and
+    in at least one flow, as for uniform values.
+
+    subn: no condition on differences can hold. The values are integers times 2^-1074 below 50
+    in magnitude, so every sum and difference of the rule is exact (no row reaches 2^52 of
+    them) and only the quotient by d + 1 rounds: the bits do not depend on the order of any
+    row, which is asserted here so that nobody reads a subn pass as evidence about order. What
+    subn brings to reordered rows is signed zeros through every gather and store: the oracle
+    holds -0.0 in the estimate or a flow of at least one named row.
+
+    huge: "every named row" cannot hold either. A row whose chain overflows in both orders ends
+    in the same infinity, or in NaN once both infinities met, whatever the order (10 of the 12
+    cases have such named rows at every seed from 3 to 12). The family exists for the other
+    rows, where the order decides whether and where the chain overflows: at least one named
+    row differs in its estimate or a flow, and at least one row of three or more slots of the
+    graph is of another class (finite, +inf, -inf, NaN) than on ascending rows; the class
+    condition on the named rows is test_huge_changes_the_class_of_a_named_row."""
+    rows = _named(name)
+    da, df = oc.differing_rows(name, how, family)
+    if family == "subn":
+        assert not da.any() and not df.any(), (name, how, "subn sums are exact")
+        nz = oc.neg_zero_rows(name, how)
+        assert any(nz[i] for i in rows), (name, how, "no named row reaches -0.0")
+    elif family == "huge":
+        assert any(da[i] or df[i] for i in rows), (name, how, "no named row differs")
+        cc = oc.class_changing_rows(name, how)
+        assert cc[oc.base_graph(name).degrees >= 3].any(), (name, how, "no row changes class")
+        ref = oc.reference(name, how, None, family)
+        last = oc.stops(name, family)[-1]
+        assert np.isnan(ref[last][0]).any() and np.isinf(ref[3][1]).any()  # the chains do overflow
+    else:
+        for i in rows:
+            assert da[i], (name, how, family, oc.named_rows(name)[i], "estimate")
+            assert df[i], (name, how, family, oc.named_rows(name)[i], "flows")
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_huge_changes_the_class_of_a_named_row(name):
+    """Over the named rows of the case at least one is finite, +inf, -inf or NaN under a
+    reordered oracle where the ascending one is of another class, at one of the early stops: an
+    engine that summed that row in ascending order would put an infinity or a NaN where the
+    reference has none. Two cases have no such seed from 3 to 12 (order_cases.HUGE_BITWISE_ONLY);
+    for them the test states that, so that a change of their named rows or seeds revisits it."""
+    rows = _named(name)
+    hit = [how for how in oc.GPU_HOWS[name] if any(oc.class_changing_rows(name, how)[i] for i in rows)]
+    assert bool(hit) == (name not in oc.HUGE_BITWISE_ONLY), (name, hit)
+    assert len(oc.HUGE_BITWISE_ONLY) <= 2
+
+
+def test_family_table_and_stops():
+    """The table both sides parametrize from: wide, huge and subn on every case, the packing
+    families on pack_er only; huge stops at rounds 1, 2, 3 and the case's last stop, every other
+    family at the case's stops; the uniform seeds are the ones fixed before."""
+    assert set(oc.GPU_FAMILIES) == set(oc.GRAPHS) == set(oc.GPU_HOWS)
+    for name, fams in oc.GPU_FAMILIES.items():
+        assert fams[:3] == ("wide", "huge", "subn")
+        assert fams[3:] == (("neg", "sym", "binade") if name == "pack_er" else ())
+        assert oc.stops(name, "huge")[:3] == (1, 2, 3) and oc.stops(name, "huge")[-1] == oc.STOPS[name][-1]
+        assert len(oc.stops(name, "huge")) <= 4
+        for family in fams:
+            assert 3 <= oc.VALUE_SEED[name, family] <= 12
+            if family != "huge":
+                assert oc.stops(name, family) == oc.STOPS[name]
+    assert len(oc.FAMILY_TRIPLES) == len(set(oc.FAMILY_TRIPLES)) == 72
+    assert {n: oc.VALUE_SEED[n] for n in oc.GRAPHS} == {**{n: 3 for n in oc.GRAPHS}, "batch_boundary": 4,
+                                                        "rmat_large": 5, "tile_limit": 6, "pack_er": 4}
+
+
+def test_pack_family_inputs_reach_every_width():
+    """The inputs of test_packed_families_on_reordered_rows, from the oracle and the plan's rule
+    restated (pack_cases.plan_of) alone: on the reordered pack_er graph with the non-finite
+    components beside it, the plan from the oracle's estimates gives 32, 16 and 8 bits at the
+    three stops of parity_util.PACK_STOPS, for each packing family; the components end in
+    NaN and -0.0 (the doubles behind the escape code); and the straddle input packs to 8 bits
+    from the first plan."""
+    from pack_cases import plan_of, plan_sample
+    from parity_util import count_neg_zero
+    from parity_util import PACK_STOPS
+
+    for family in oc.PACK_FAMILIES:
+        g, v = oc.pack_graph(family)
+        sample = plan_sample(g.col)
+        refs = oc.pack_reference(family)
+        n0 = oc.base_graph("pack_er").n
+        for stop, width in zip(PACK_STOPS[family], (32, 16, 8)):
+            for r in (stop - oc.PACK_SETTLED, stop):  # pack_every 4: a plan from this span is in use at the stop
+                assert plan_of(refs[r][0], sample)[0] == width, (family, r)
+        a_end = refs[PACK_STOPS[family][-1]][0]
+        assert np.isfinite(a_end[:n0]).all()
+        assert np.isnan(a_end[n0:]).sum() == 9 and count_neg_zero(a_end[n0:]) == 1
+    g, v = oc.graph("pack_er", "random"), oc.straddle_values()
+    a, _ = coracle.ca_sync(*g.arrays(), v, 2)
+    assert plan_of(a, plan_sample(g.col))[0] == 8
+
+
+def _rule_on_python_floats(adj, v, rounds, drop_zero_sign):
+    """[(estimates, flows in row order)] after 1 .. rounds rounds of the collect-all rule on a
+    small graph (round 0 receives nothing; from round 1 on fr = -f_ji, er = a_j, S = 0.0 + fr..,
+    T = 0.0 + er.., a = ((v - S) + T) / (d + 1), f_ij = (fr + a) - er). drop_zero_sign: a gathered
+    estimate that is a zero arrives as +0.0."""
+    n = len(v)
+    f = {(i, j): 0.0 for i in range(n) for j in adj[i]}
+    a, out = [0.0] * n, []
+    for r in range(rounds):
+        na, nf = [0.0] * n, {}
+        for i in range(n):
+            S = T = 0.0
+            got = []
+            for j in adj[i]:
+                fr, er = (-f[j, i] if r else 0.0), a[j]
+                if drop_zero_sign and er == 0.0:
+                    er = er + 0.0
+                got.append((j, fr, er))
+                S, T = S + fr, T + er
+            na[i] = ((v[i] - S) + T) / (len(adj[i]) + 1)
+            for j, fr, er in got:
+                nf[i, j] = (fr + na[i]) - er
+        a, f = na, nf
+        out.append((np.array(a), np.array([f[i, j] for i in range(n) for j in adj[i]])))
+    return out
+
+
+def test_signed_zero_extras_show_the_sign_of_a_gathered_zero():
+    """The components of order_cases.SIGNED_ZERO_EXTRAS, alone: the rule on Python floats equals
+    the C oracle on them, and a gather that drops the sign of a zero gives other bits at every
+    packing stop of the `neg` case or one or two rounds after the last (the stops of
+    test_packed_escapes_keep_the_sign_of_zero), so a packed reader that loses the sign behind
+    its escape code fails there."""
+    from parity_util import PACK_STOPS
+
+    stops = oc.pack_stops("neg", "signed_zero")
+    assert stops[-3:] == (PACK_STOPS["neg"][-1], PACK_STOPS["neg"][-1] + 1, PACK_STOPS["neg"][-1] + 2)
+    for comp in oc.SIGNED_ZERO_EXTRAS:
+        adj = [[1], [0]] if len(comp) == 2 else [[2, 1], [0, 2], [1, 0]]  # with_components' rows
+        rp = np.cumsum([0] + [len(x) for x in adj]).astype(np.int64)
+        g = fu.Graph.from_csr(rp, np.concatenate(adj).astype(np.int32))
+        right = _rule_on_python_floats(adj, comp, stops[-1], False)
+        wrong = _rule_on_python_floats(adj, comp, stops[-1], True)
+        differ = []
+        for r in stops:
+            a, f = coracle.ca_sync(*g.arrays(), np.array(comp), r)
+            assert np.array_equal(_bits(a), _bits(right[r - 1][0])) and np.array_equal(_bits(f), _bits(right[r - 1][1])), (comp, r)
+            differ.append(not np.array_equal(_bits(f), _bits(wrong[r - 1][1])))
+        assert any(differ[len(oc.STOPS["pack_er"]):len(oc.STOPS["pack_er"]) + 3]), (comp, differ)  # at a packing stop
+        assert any(differ[-3:]), (comp, differ)
+
+
 @pytest.mark.parametrize("name,how", [("rmat_small", "random"), ("rmat_small", "descending"), ("tile_limit", "zigzag"),
                                       ("pair_class", "random"), ("batch_boundary", "rotated")])
 def test_python_oracle_equals_c_oracle_off_ascending_rows(name, how):

@@ -19,7 +19,8 @@ import pytest
 
 import coracle
 import fu
-from parity_util import FAMILIES, _class_edge_graph, assert_same_bits, count_neg_zero
+from parity_util import (FAMILIES, FINITE_EXTRAS, NONFINITE_EXTRAS, PACK_STOPS, PACK_WIDTHS, _class_edge_graph,
+                         assert_same_bits, count_neg_zero)
 
 pytestmark = pytest.mark.gpu
 
@@ -138,24 +139,7 @@ def test_packing_window_straddles_signed_zero(kernel):
 # ------------------------------------------------------------------------------------
 # 3. packing on other signs and binades, non-finite values behind the escape code
 # ------------------------------------------------------------------------------------
-# components beside the giant one; their estimates never enter the packed window
-NONFINITE_EXTRAS = [(np.inf, 1.0), (-np.inf, np.inf), (np.nan, 2.0), (-0.0, -0.0), (5e-324, -5e-324),
-                    (1.7e308, 1.7e308, 1.7e308)]
-FINITE_EXTRAS = [(-0.0, -0.0), (5e-324, -5e-324), (3.0, -7.0, 1e-300)]
 GIANT_N, GIANT_SEED = 20_000, 17
-
-# Total rounds at which each case stops. The widths come from the plan's rule (centre: the
-# median key of the first 64 sampled gather targets; the narrowest width whose window holds
-# 99.5 % of the 4096 sampled keys) applied on the CPU to the C oracle's estimates before
-# every 4th round: the round whose plan first gives 32 / 16 / 8 bits is
-#   neg 108 / 192 / 236, sym 144 / 228 / 272, binade 104 / 188 / 232, wide 160 / 244 / never.
-# `wide` stays at 16 bits (checked to round 1200, and for two other seeds): the flows of the
-# nodes whose value is near 2^60 carry roundings of up to 2^8, which leave those nodes'
-# estimates, and their neighbours', thousands of ulps from a mean near 2^46; about 6 % of
-# the values lie above 2^53, far more than the 0.5 % the 8-bit window may miss.
-PACK_STOPS = {"neg": (160, 220, 300), "sym": (200, 256, 320), "binade": (160, 220, 300),
-              "wide": (200, 280, 340)}
-PACK_WIDTHS = {"neg": {32, 16, 8}, "sym": {32, 16, 8}, "binade": {32, 16, 8}, "wide": {32, 16}}
 
 
 def _giant_with_extras(values, extras):
