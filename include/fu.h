@@ -95,7 +95,16 @@ int fu_values_uniform(int64_t n, uint64_t seed, double lo, double hi, double *ou
  * ==================================================================================== */
 typedef struct fu_handle fu_handle;
 
-/* rowptr[n+1], col[e], rev[e] (rev may be NULL: computed natively), value[n]. */
+/* rowptr[n+1], col[e], rev[e] (rev may be NULL: computed natively), value[n].
+ * Arguments are checked before any HIP call and before any array is walked, also on a host
+ * without a GPU: the scalars, e, rowptr's ends, rowptr monotone, col in range (FU_ERR_ARG),
+ * then the graph (FU_ERR_GRAPH); fu_dist_create(_local) report a bad local CSR under the
+ * same "fu_create: ..." texts.
+ * A row that holds its own id is refused by every entry point that takes raw arrays (this
+ * one, fu_batch_create, fu_lossy_create(_k), fu_churn_create(_k), fu_pair_create,
+ * fu_dist_create(_local) for a local column equal to its local row, fu_churn_live,
+ * fu_pair_matching) as fu_graph_from_csr refuses it: FU_ERR_GRAPH, "<entry point>: self-loop
+ * at node i" (both partitioned entry points say "fu_dist_create"). */
 int fu_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
               const int32_t *rev, const double *value, int32_t device, fu_handle **out);
 int fu_create_from_graph(const fu_graph *g, const double *value, int32_t device,

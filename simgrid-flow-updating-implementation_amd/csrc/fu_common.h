@@ -54,8 +54,23 @@ int build_rev(fu_graph &g);
 
 // What fu_batch_create, fu_lossy_create and fu_pair_create ask of a caller's CSR, on the host
 // and before any HIP call; `who` is the entry point's name, for the message.
-// rowptr[0] == 0, rowptr[n] == e, rowptr monotone, every col in [0, n).
+// rowptr[0] == 0, rowptr[n] == e, rowptr monotone, every col in [0, n), all FU_ERR_ARG; then no
+// row holds its own id (FU_ERR_GRAPH, "<who>: self-loop at node i": fu_graph_from_csr's rule).
+// No array is read past what the checks before it have proved to be there.
 int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col);
+// The same for one rank's rows of a partition: columns run to ncols = n_local + n_ghost_a (a
+// ghost column is never a self-loop), and the self-loop text carries loop_who.
+int check_csr_cols(const char *who, const char *loop_who, int32_t n, int64_t ncols, int64_t e, const int64_t *rowptr,
+                   const int32_t *col);
+// Everything fu_create, fu_create_from_graph and fu_dist_create(_local) ask of their arguments
+// ahead of the device probe, in this order: the null, n and e checks, e < INT32_MAX - 64, then
+// check_csr_cols with the texts under "fu_create" and ncols = n + a_extra.
+int check_create(const char *loop_who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                 const double *value, int32_t a_extra, const void *out);
+// All of fu_create's checks: check_create, then symmetry: a caller's rev as check_rev(kSymmetric),
+// none as rev_of_csr's verdict.
+int check_fu_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                    const double *value, const void *out);
 // rev against a CSR that passed check_csr. kSymmetric: rev[k] lies in the row of k's neighbour
 // at a slot that points back, which proves the graph symmetric (the batched engine never reads
 // rev on the device). kPairing: rev is an involution as well (the lossy and pairwise engines
@@ -65,6 +80,10 @@ int check_rev(const char *who, RevCheck level, int32_t n, const int64_t *rowptr,
 // build_rev for a caller's CSR: the reverse-edge index in *rev, or with rev == nullptr only
 // the verdict (FU_ERR_GRAPH if some i -> j lacks its j -> i).
 int rev_of_csr(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, std::vector<int32_t> *rev);
+// The engines that gather through rev (lossy, churn, pairwise), before their first HIP call:
+// the CSR checked, *rev built into *built where the caller gave none, and checked as a pairing.
+int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                const int32_t **rev, std::vector<int32_t> *built);
 }  // namespace fu
 
 #define FU_TRY_BEGIN try {

@@ -229,6 +229,8 @@ static int dist_create(int32_t n_local, int64_t e_local, const int64_t *rowptr, 
   const int64_t nsa = send_a_off[nranks];
   for (int64_t q = 0; q < nsa; ++q)
     if (send_a_idx[q] < 0 || send_a_idx[q] >= n_local) return fail(FU_ERR_ARG, "fu_dist_create: send_a_idx out of range");
+  // the local CSR: columns run over the local rows and the ghost estimate slots
+  if (int rc = fu::check_create("fu_dist_create", n_local, e_local, rowptr, col, value, n_ghost_a, out)) return rc;
   fu_handle *h = nullptr;
   if (int rc = fu__create_common(n_local, e_local, rowptr, col, value, device, n_ghost_a, &h)) return rc;
   auto *d = new DistState();

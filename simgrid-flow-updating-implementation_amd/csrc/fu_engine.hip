@@ -2538,13 +2538,11 @@ int fu_device_count(int32_t *out) {
 // Internal constructor shared by fu_create / fu_dist_create: uploads the local CSR. The
 // kernels never read a reverse-edge index (flows are reconstructed, kernel 4 §4.1), so only
 // rowptr, col and the values go to the device. a_extra: ghost estimate slots (multi-GPU).
+// The arguments have passed fu::check_create (every caller runs it first): the device probe
+// is the first thing here, so a bad array is reported on a host without a GPU too.
 int fu__create_common(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
                       const double *value, int32_t device, int32_t a_extra, fu_handle **out) {
   FU_TRY_BEGIN
-  if (!out || n <= 0 || e < 0 || !rowptr || !value || (e > 0 && !col) || a_extra < 0)
-    return fail(FU_ERR_ARG, "fu_create: bad arguments");
-  if (e >= (int64_t)INT32_MAX - 64) return fail(FU_ERR_ARG, "fu_create: more than 2^31-1 edges");
-  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, "fu_create: rowptr[0] must be 0 and rowptr[n] == e");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FU_ERR_HIP, "fu_create: no HIP device visible");
   if (device < 0 || device >= ndev) return fail(FU_ERR_ARG, "fu_create: device out of range");
@@ -2558,20 +2556,11 @@ int fu__create_common(int32_t n, int64_t e, const int64_t *rowptr, const int32_t
   int32_t md = 0;
   for (int32_t i = 0; i <= n; ++i) {
     rp32[i] = (int32_t)rowptr[i];
-    if (i < n) {
-      if (rowptr[i + 1] < rowptr[i]) { delete h; return fail(FU_ERR_ARG, "fu_create: rowptr not monotone"); }
-      md = std::max<int32_t>(md, (int32_t)(rowptr[i + 1] - rowptr[i]));
-    }
+    if (i < n) md = std::max<int32_t>(md, (int32_t)(rowptr[i + 1] - rowptr[i]));
   }
   h->max_deg = md;
   const int32_t na = n + a_extra;
   h->na = na;
-  for (int64_t k = 0; k < e; ++k) {
-    if (col[k] < 0 || col[k] >= na) {
-      delete h;
-      return fail(FU_ERR_ARG, "fu_create: col index out of range at edge " + std::to_string(k));
-    }
-  }
   int rc = FU_OK;
   auto cleanup = [&](int code) { fu_destroy(h); return code; };
   if ((rc = set_device(h))) return cleanup(rc);
@@ -2645,39 +2634,26 @@ int fu__create_common(int32_t n, int64_t e, const int64_t *rowptr, const int32_t
   FU_TRY_END
 }
 
-// The flow reconstruction needs every i -> j to have its j -> i: a caller's rev is checked to
-// be that pairing; without one, fu::build_rev checks symmetry (the index itself is not kept).
+// Every argument and CSR check (fu::check_fu_create) comes before anything walks the arrays. The
+// flow reconstruction needs every i -> j to have its j -> i: a caller's rev is checked to be
+// that pairing; without one, fu::build_rev checks symmetry (the index itself is not kept).
 int fu_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
               const int32_t *rev, const double *value, int32_t device, fu_handle **out) {
   FU_TRY_BEGIN
-  if (!rowptr || n <= 0 || e < 0 || (e > 0 && !col)) return fail(FU_ERR_ARG, "fu_create: bad arguments");
-  if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, "fu_create: rowptr[0] must be 0 and rowptr[n] == e");
-  if (e > 0 && !rev) {
-    fu_graph g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + e);
-    if (int rc = fu::build_rev(g)) return rc;
-  } else if (e > 0) {
-    for (int32_t i = 0; i < n; ++i)
-      for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-        const int32_t j = col[k];
-        const int64_t r = rev[k];
-        if (j < 0 || j >= n || r < rowptr[j] || r >= rowptr[j + 1] || col[r] != i)
-          return fail(FU_ERR_GRAPH, "fu_create: rev is not the reverse-edge pairing (the graph must be symmetric) at edge " +
-                                        std::to_string(k));
-      }
-  }
+  if (int rc = fu::check_fu_create(n, e, rowptr, col, rev, value, out)) return rc;
   return fu__create_common(n, e, rowptr, col, value, device, 0, out);
   FU_TRY_END
 }
 
 int fu_create_from_graph(const fu_graph *g, const double *value, int32_t device,
                          fu_handle **out) {
+  FU_TRY_BEGIN
   if (!g) return fail(FU_ERR_ARG, "fu_create_from_graph: NULL graph");
   const int64_t E = g->rowptr[g->n];
   if ((int64_t)g->rev.size() != E) return fail(FU_ERR_GRAPH, "fu_create_from_graph: graph is not symmetric");
+  if (int rc = fu::check_create("fu_create_from_graph", g->n, E, g->rowptr.data(), g->col.data(), value, 0, out)) return rc;
   return fu__create_common(g->n, E, g->rowptr.data(), g->col.data(), value, device, 0, out);
+  FU_TRY_END
 }
 
 int fu_create_from_graph_ex(const fu_graph *g, const double *value, int32_t device,

@@ -131,14 +131,38 @@ int build_rev(fu_graph &g) {
   return FU_OK;
 }
 
-int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col) {
+int check_csr_cols(const char *who, const char *loop_who, int32_t n, int64_t ncols, int64_t e, const int64_t *rowptr,
+                   const int32_t *col) {
   const std::string w(who);
   if (rowptr[0] != 0 || rowptr[n] != e) return fail(FU_ERR_ARG, w + ": rowptr[0] must be 0 and rowptr[n] == e");
+  // rowptr[0] == 0, rowptr[n] == e and monotone: every rowptr[i] lies in [0, e]
   for (int32_t i = 0; i < n; ++i)
     if (rowptr[i + 1] < rowptr[i]) return fail(FU_ERR_ARG, w + ": rowptr not monotone");
   for (int64_t q = 0; q < e; ++q)
-    if (col[q] < 0 || col[q] >= n) return fail(FU_ERR_ARG, w + ": col index out of range at edge " + std::to_string(q));
+    if (col[q] < 0 || col[q] >= ncols) return fail(FU_ERR_ARG, w + ": col index out of range at edge " + std::to_string(q));
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+      if (col[k] == i) return fail(FU_ERR_GRAPH, std::string(loop_who) + ": self-loop at node " + std::to_string(i));
   return FU_OK;
+}
+
+int check_csr(const char *who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col) {
+  return check_csr_cols(who, who, n, n, e, rowptr, col);
+}
+
+int check_create(const char *loop_who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                 const double *value, int32_t a_extra, const void *out) {
+  if (!out || n <= 0 || e < 0 || !rowptr || !value || (e > 0 && !col) || a_extra < 0)
+    return fail(FU_ERR_ARG, "fu_create: bad arguments");
+  if (e >= (int64_t)INT32_MAX - 64) return fail(FU_ERR_ARG, "fu_create: more than 2^31-1 edges");
+  return check_csr_cols("fu_create", loop_who, n, (int64_t)n + a_extra, e, rowptr, col);
+}
+
+int check_fu_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                    const double *value, const void *out) {
+  if (int rc = check_create("fu_create", n, e, rowptr, col, value, 0, out)) return rc;
+  if (e == 0) return FU_OK;
+  return rev ? check_rev("fu_create", RevCheck::kSymmetric, n, rowptr, col, rev) : rev_of_csr(n, e, rowptr, col, nullptr);
 }
 
 int check_rev(const char *who, RevCheck level, int32_t n, const int64_t *rowptr, const int32_t *col, const int32_t *rev) {
@@ -161,6 +185,17 @@ int rev_of_csr(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, 
   if (int rc = build_rev(g)) return rc;
   if (rev) rev->swap(g.rev);
   return FU_OK;
+}
+
+int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                const int32_t **rev, std::vector<int32_t> *built) {
+  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, who + ": more than 2^31-1 directed edges (rev is int32)");
+  if (int rc = check_csr(who.c_str(), n, e, rowptr, col)) return rc;
+  if (e > 0 && !*rev) {
+    if (int rc = rev_of_csr(n, e, rowptr, col, built)) return rc;
+    *rev = built->data();
+  }
+  return check_rev(who.c_str(), RevCheck::kPairing, n, rowptr, col, *rev);
 }
 
 }  // namespace fu

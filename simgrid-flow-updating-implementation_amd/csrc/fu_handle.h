@@ -121,19 +121,6 @@ int err_slots(H *h, int64_t count) {
   return FU_OK;
 }
 
-// The engines that gather through rev (lossy, churn, pairwise), before their first HIP call:
-// the CSR checked, *rev built into *built where the caller gave none, and checked as a pairing.
-inline int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
-                       const int32_t **rev, std::vector<int32_t> *built) {
-  if (e > (int64_t)INT32_MAX) return fail(FU_ERR_ARG, who + ": more than 2^31-1 directed edges (rev is int32)");
-  if (int rc = check_csr(who.c_str(), n, e, rowptr, col)) return rc;
-  if (e > 0 && !*rev) {
-    if (int rc = rev_of_csr(n, e, rowptr, col, built)) return rc;
-    *rev = built->data();
-  }
-  return check_rev(who.c_str(), RevCheck::kPairing, n, rowptr, col, *rev);
-}
-
 // *_create, after every check on the arguments: the device, the stream and the events. On an
 // error the caller destroys the handle.
 template <typename H>

@@ -29,6 +29,10 @@ PATH_REV = np.array([1, 0, 3, 2], dtype=np.int32)
 DOUBLED_RP = np.array([0, 2, 4], dtype=np.int64)
 DOUBLED_COL = np.array([1, 1, 0, 0], dtype=np.int32)
 DOUBLED_REV = np.array([2, 2, 0, 1], dtype=np.int32)
+# two nodes, each with a loop and the edge to the other; rev pairs each loop with itself
+LOOPS_RP = np.array([0, 2, 4], dtype=np.int64)
+LOOPS_COL = np.array([0, 1, 0, 1], dtype=np.int32)
+LOOPS_REV = np.array([0, 2, 1, 3], dtype=np.int32)
 
 
 def _p(a):
@@ -96,6 +100,13 @@ CREATE_ROWS = [
     ("rev too large", dict(rp=PATH_RP, col=PATH_COL, rev=_arr([1, 0, 4, 2], np.int32)), _REV + "2", GRAPH),
     ("rev negative", dict(rp=PATH_RP, col=PATH_COL, rev=_arr([-1, 0, 3, 2], np.int32)), _REV + "0", GRAPH),
     ("rev into the wrong row", dict(rp=PATH_RP, col=PATH_COL, rev=_arr([3, 2, 1, 0], np.int32)), _REV + "0", GRAPH),
+    # a row that holds its own id: fu_graph_from_csr's rule, for raw arrays too
+    ("self-loop", dict(rp=PATH_RP, col=_arr([1, 1, 2, 1], np.int32), rev=None), "self-loop at node 1", GRAPH),
+    ("self-loop, with a rev", dict(rp=PATH_RP, col=_arr([1, 1, 2, 1], np.int32), rev=PATH_REV), "self-loop at node 1", GRAPH),
+    # both loops paired with themselves, an involution: every rev check would pass
+    ("self-loops, rev[k] == k", dict(rp=LOOPS_RP, col=LOOPS_COL, rev=LOOPS_REV), "self-loop at node 0", GRAPH),
+    ("self-loop on the last row", dict(rp=_arr([0, 1, 4], np.int64), col=_arr([1, 0, 1, 1], np.int32), rev=None),
+     "self-loop at node 1", GRAPH),
 ]
 
 
@@ -117,6 +128,23 @@ def test_more_edges_than_an_int32_rev_holds(eng):
     assert got == (ARG, f"fu_{eng}_create: {tail}")
     if eng != "batch":  # 2^31 - 1 itself passes that check and fails the next
         assert _create(eng, PATH_RP, PATH_COL, None, e=2 ** 31 - 1) == (ARG, f"fu_{eng}_create: {_ROWPTR}")
+
+
+@pytest.mark.parametrize("eng", ("lossy", "churn"))
+def test_self_loop_through_the_k_column_creates(eng):
+    """fu_lossy_create_k and fu_churn_create_k share the front half of the one-column creates."""
+    v = np.ones((2, 3))
+    h = L.vp()
+    rc = getattr(L.lib, f"fu_{eng}_create_k")(2, 4, _p(LOOPS_RP), _p(LOOPS_COL), _p(LOOPS_REV), 3, _p(v), 0, ctypes.byref(h))
+    assert (rc, L.last_error()) == (GRAPH, f"fu_{eng}_create_k: self-loop at node 0")
+
+
+def test_churn_live_refuses_a_self_loop():
+    out, alive = np.zeros(4, dtype=np.uint8), np.ones(2, dtype=np.uint8)
+    for rev in (LOOPS_REV, None):
+        rc = L.lib.fu_churn_live(2, _p(LOOPS_RP), _p(LOOPS_COL), _p(rev), _p(alive), None, _p(out))
+        assert (rc, L.last_error()) == (GRAPH, "fu_churn_live: self-loop at node 0")
+    assert not out.any()  # nothing written
 
 
 @pytest.mark.parametrize("k", [0, 17, -1])
@@ -218,4 +246,6 @@ def test_pair_matching_bad_arguments():
     assert call(col=None) == bad
     assert call(rp=_arr([0, 3, 1, 4], np.int64)) == (ARG, "fu_pair_matching: rowptr not monotone")
     assert call(col=_arr([3, 0, 2, 1], np.int32)) == (ARG, "fu_pair_matching: col index out of range at edge 0")
+    assert call(col=_arr([1, 0, 2, 2], np.int32)) == (GRAPH, "fu_pair_matching: self-loop at node 2")
+    assert call(n=2, rp=LOOPS_RP, col=LOOPS_COL) == (GRAPH, "fu_pair_matching: self-loop at node 0")
     assert call()[0] == 0
