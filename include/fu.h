@@ -459,6 +459,24 @@ int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *c
                    const int32_t *rev, const double *value, int32_t device, fu_pair **out);
 int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t device,
                               fu_pair **out);
+/* K value columns over one graph and one matching, 1 <= k <= 16 (else FU_ERR_ARG): value[n*k],
+ * node-major (value[i*k + c]). One message carries all k (flow, estimate) pairs, so the matching
+ * of a round, the three loss outcomes of a pair, the link mask, the statistics and the loss
+ * statistics are per handle, exactly those of a handle of one column with the same graph and
+ * seeds, and column c (last, f and c after every round) is bit-equal to a fu_pair_create handle
+ * run on column c alone; no arithmetic crosses columns. On such a handle every entry point below
+ * works with arrays scaled as for fu_lossy_create_k: set_values, set_targets and get_estimates
+ * take or return n*k doubles (x[i*k + c]), get_flows and get_cache return e*k doubles
+ * (f[slot*k + c], the caller's slot order), the error trace has (rounds / err_every) * k entries,
+ * round-major, max_err writes out[k] (a NaN raises only its own column's entry), and the link
+ * mask stays e bytes. A handle made here with k = 1 is bit-equal to one of fu_pair_create. */
+int fu_pair_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
+                     const int32_t *rev, int32_t k, const double *value /* n*k */, int32_t device,
+                     fu_pair **out);
+int fu_pair_create_from_graph_k(const fu_graph *g, int32_t k, const double *value,
+                                int32_t device, fu_pair **out);
+/* The handle's number of columns (1 for fu_pair_create). */
+int fu_pair_get_columns(fu_pair *h, int32_t *k);
 /* Seed of the matchings of the rounds run after the call (default 0). */
 int fu_pair_set_seed(fu_pair *h, uint64_t seed);
 /* Loss probability and seed of the rounds run after the call (defaults 0, 0). p outside [0, 1]
@@ -471,7 +489,8 @@ int fu_pair_set_link_mask(fu_pair *h, const uint8_t *down);
  * proposal (default), 1 = every listener hashes its own row. Same matching, same bits; the
  * switch exists for the A/B of tools/bench_pair.py. Unknown key or value: FU_ERR_ARG. */
 int fu_pair_set_option(fu_pair *h, const char *key, int64_t value);
-/* The inputs change (value[n]); flows, caches, last averages and the round counter are kept. */
+/* The inputs change (value[n], or value[n*k]); flows, caches, last averages and the round counter
+ * are kept. */
 int fu_pair_set_values(fu_pair *h, const double *value);
 /* Zero the state, the round counter and the statistics (the loss counters too). The seeds, the
  * loss, the mask and the values are kept. */
@@ -483,14 +502,15 @@ int fu_pair_reset(fu_pair *h);
 int fu_pair_run(fu_pair *h, int32_t rounds, int32_t err_every, double *err_trace);
 /* Same rounds, timed with HIP events on the handle's stream (synchronises). */
 int fu_pair_run_timed(fu_pair *h, int32_t rounds, float *ms);
-int fu_pair_set_targets(fu_pair *h, const double *target /* n */);
-/* max_i |last_i - target_i| on the current state (synchronises). */
+int fu_pair_set_targets(fu_pair *h, const double *target /* n, or n*k */);
+/* max_i |last_i - target_i| on the current state, out[k] per column on a handle of k columns
+ * (synchronises). */
 int fu_pair_max_err(fu_pair *h, double *out);
 /* last[n]: every node's average at its last fire (0.0 for a node that has not fired). */
-int fu_pair_get_estimates(fu_pair *h, double *last_out /* n */);
-int fu_pair_get_flows(fu_pair *h, double *f_out /* e */);
+int fu_pair_get_estimates(fu_pair *h, double *last_out /* n, or n*k */);
+int fu_pair_get_flows(fu_pair *h, double *f_out /* e, or e*k */);
 /* c[e]: the cached estimate of every slot. */
-int fu_pair_get_cache(fu_pair *h, double *c_out /* e */);
+int fu_pair_get_cache(fu_pair *h, double *c_out /* e, or e*k */);
 int fu_pair_get_round(fu_pair *h, int64_t *rounds_done);
 /* out[0] = pairs exchanged since the last reset, out[1] = nodes that have never fired since
  * then. Synchronises. */

@@ -42,8 +42,18 @@
 // two chains), then kp_heavy for the pairs with a row above kLightDeg (one block per pair, the
 // rows in LDS chunks, thread 0 carrying). Nothing in a round waits for the host.
 //
+// A handle of K value columns (fu_pair_create_k) keeps v and last node-major
+// (x[i * K + c]) and f and c edge-major (f[k * K + c]). The matching, the loss decisions, the
+// heavy list, `fired` and the counters are per handle, as for one column; column c follows the
+// exchange above on its own and no arithmetic crosses columns. Such a handle runs kp_propose or
+// kp_scan as they are, then kp_exchange_cols (lane l of a pair's group carries columns l and
+// l + 8 and reads its rows straight from memory) and kp_heavy_cols (threads 0 .. K-1 carry a
+// column each through chunks of kColsChunk / K slots).
+//
 // The handle scaffold (create and destroy, the run loops, the error slots and k_max_err, the
-// small entry points) is csrc/fu_handle.h, shared with the batched and lossy engines.
+// small entry points) is csrc/fu_handle.h, shared with the batched and lossy engines; the
+// per-column error reduction k_max_err_cols is csrc/fu_cols_err.h, shared with the rev-gather round.
+#include "fu_cols_err.h"
 #include "fu_handle.h"
 
 using namespace fu;
@@ -56,6 +66,10 @@ constexpr int kGroups = kBlock / kGroup;    // pairs a block works on at once
 constexpr int kLightDeg = 64;               // a pair with a row above this degree goes to kp_heavy
 constexpr int kChunk = 1024;                // kp_heavy: flows staged in LDS per chunk
 constexpr int kHeavyBlocks = 1024;          // kp_heavy: at most this many blocks share the round's heavy pairs
+constexpr int kColsChunk = 2048;            // kp_heavy_cols: doubles staged in LDS per chunk, kColsChunk / K slots
+constexpr int kColsBatch = 8;               // kp_exchange_cols: a lane's loads of one column in flight before the adds
+static_assert(kMaxCols <= 2 * kGroup, "a lane of a group carries at most two columns");
+static_assert(kColsChunk / kMaxCols >= 1, "a chunk holds a slot at every K");
 
 // The lost-message counters: kLostLines pairs (first messages lost, answers lost), a 128-byte
 // line each; block b adds into pair b % kLostLines and fu_pair_get_loss_stats sums them. With
@@ -366,6 +380,242 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(Args A) {
   }
 }
 
+// ---- K value columns ------------------------------------------------------------------------
+// The sums of one row for a lane's two columns: S0 = 0.0 + p[0], p[K], .. and S1 the same from
+// p + kGroup (only if `two`), in row order; slot `sub` of the row counts as (r0, r1) in place of
+// what is stored (-1: no slot). The loads do not depend on the adds, so kColsBatch slots of both
+// columns are in flight before the first add of a batch.
+__device__ inline void row_sums(const double *__restrict__ p, int deg, int K, bool two, int sub, double r0, double r1,
+                                double &S0, double &S1) {
+  S0 = 0.0;
+  S1 = 0.0;
+  for (int d0 = 0; d0 < deg; d0 += kColsBatch) {
+    double x0[kColsBatch], x1[kColsBatch];
+#pragma unroll
+    for (int u = 0; u < kColsBatch; ++u) {
+      const int d = d0 + u;
+      x0[u] = d < deg ? p[(int64_t)d * K] : 0.0;
+      x1[u] = d < deg && two ? p[(int64_t)d * K + kGroup] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kColsBatch; ++u) {
+      const int d = d0 + u;
+      if (d < deg) {
+        S0 = S0 + (d == sub ? r0 : x0[u]);
+        S1 = S1 + (d == sub ? r1 : x1[u]);
+      }
+    }
+  }
+}
+
+// kp_exchange for K columns: the same compaction of the block's matched listeners and the same
+// group of 8 lanes per pair. Lane l of a group carries columns l and l + 8 of its pair through
+// both chains. Nothing is staged in LDS: at K columns the two rows of kGroups pairs do not fit
+// it, the loads of a row do not depend on the adds, and across the lanes of a group the loads of
+// f[(b + d) * K + c] are contiguous, as are the writes of f, c and last. So the q0 loop has no
+// barrier, and a lane without a column (l >= K) sits a pair out. Lane 0 writes `fired`, lists a
+// heavy pair and counts the lost messages: once per pair, as in kp_exchange.
+template <class Args>
+__global__ __launch_bounds__(kBlock) void kp_exchange_cols(Args A, int K) {
+  constexpr bool kLossy = Args::kLossy;
+  __shared__ int2 s_pair[kBlock];
+  __shared__ int s_cnt[kBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t node = (int64_t)blockIdx.x * kBlock + tid;
+  u64 word = kNone;
+  if (node < A.n) {
+    word = A.word[node];
+    if (word != kNone) A.word[node] = kNone;
+  }
+  const bool matched = word != kNone;
+  const u64 bal = __ballot(matched);
+  if (lane == 0) s_cnt[w] = __popcll(bal);
+  __syncthreads();
+  int base = 0, np = 0;
+  for (int q = 0; q < kBlock / 64; ++q) {
+    if (q < w) base += s_cnt[q];
+    np += s_cnt[q];
+  }
+  if (matched) s_pair[base + __popcll(bal & ((1ull << lane) - 1))] = make_int2((int)(uint32_t)word, (int)node);
+  __syncthreads();
+  const int g = tid / kGroup, l = tid % kGroup;
+  const bool two = l + kGroup < K;
+  int n_lost1 = 0, n_lost2 = 0;  // kLossy: this thread's pairs (lane 0 of a group counts)
+  for (int q = g; q < np; q += kGroups) {
+    const int i = s_pair[q].x, j = s_pair[q].y;
+    const int64_t bi = A.rowptr[i], bj = A.rowptr[j];
+    const int di = (int)(A.rowptr[i + 1] - bi), dj = (int)(A.rowptr[j + 1] - bj);
+    if (di > kLightDeg || dj > kLightDeg) {
+      if (l == 0) {
+        const unsigned slot = atomicAdd(A.n_heavy, 1u);
+        if ((int64_t)slot < A.heavy_cap) A.heavy[slot] = make_int2(i, j);  // always: a heavy row is in one pair
+      }
+      continue;
+    }
+    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+    const int64_t kt = A.rev[ks];  // in row j: fu_pair_create_k checked rev as a pairing
+    bool lost1 = false, lost2 = false;
+    if constexpr (kLossy) {
+      lost1 = message_lost(A, kt);
+      lost2 = message_lost(A, ks);
+    }
+    if (l < K) {
+      // this lane's columns are l and, if `two`, l + kGroup; the second of a lane that has one
+      // is computed on zeros and never written
+      const int64_t o1 = two ? kGroup : 0;
+      double *fs = A.f + ks * K + l, *cs = A.c + ks * K + l, *li = A.last + (int64_t)i * K + l;
+      double *ft = A.f + kt * K + l, *ct = A.c + kt * K + l, *lj = A.last + (int64_t)j * K + l;
+      const double *vi = A.v + (int64_t)i * K + l, *vj = A.v + (int64_t)j * K + l;
+      const double c0 = cs[0], c1 = cs[o1], v0 = vi[0], v1 = vi[o1], f0 = fs[0], f1 = fs[o1];
+      double w0 = 0.0, w1 = 0.0;
+      if (!lost1) {
+        w0 = vj[0];
+        w1 = vj[o1];
+      }
+      double S0, S1;
+      row_sums(A.f + bi * K + l, di, K, two, -1, 0.0, 0.0, S0, S1);
+      const double ai0 = fire_avg(c0, v0, S0), ai1 = fire_avg(c1, v1, S1);
+      const double F10 = (f0 + ai0) - c0, F11 = (f1 + ai1) - c1;
+      if (kLossy && lost1) {  // i fired into a message nobody received
+        fs[0] = F10;
+        cs[0] = ai0;
+        li[0] = ai0;
+        if (two) {
+          fs[kGroup] = F11;
+          cs[kGroup] = ai1;
+          li[kGroup] = ai1;
+        }
+      } else {
+        row_sums(A.f + bj * K + l, dj, K, two, (int)(kt - bj), -F10, -F11, S0, S1);
+        const double aj0 = fire_avg(ai0, w0, S0), aj1 = fire_avg(ai1, w1, S1);
+        const double F20 = (-F10 + aj0) - ai0, F21 = (-F11 + aj1) - ai1;
+        const bool kept = kLossy && lost2;  // j answered, i never heard it: i keeps what it fired
+        fs[0] = kept ? F10 : -F20;
+        cs[0] = kept ? ai0 : aj0;
+        ft[0] = F20;
+        ct[0] = aj0;
+        li[0] = ai0;
+        lj[0] = aj0;
+        if (two) {
+          fs[kGroup] = kept ? F11 : -F21;
+          cs[kGroup] = kept ? ai1 : aj1;
+          ft[kGroup] = F21;
+          ct[kGroup] = aj1;
+          li[kGroup] = ai1;
+          lj[kGroup] = aj1;
+        }
+      }
+    }
+    if (l == 0) {
+      A.fired[i] = 1;
+      if (kLossy && lost1) {
+        n_lost1 += 1;
+      } else {
+        A.fired[j] = 1;
+        if (kLossy && lost2) n_lost2 += 1;
+      }
+    }
+  }
+  if (tid == 0 && np > 0) atomicAdd(A.pairs, (u64)np);
+  if constexpr (kLossy) {
+    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
+    block_count_to<kBlock>(n_lost1, mine);
+    __syncthreads();  // block_count_to's LDS words are read by thread 0 until here
+    block_count_to<kBlock>(n_lost2, mine + 1);
+  }
+}
+
+// kp_heavy for K columns: one block per pair, the rows staged in chunks of kColsChunk doubles,
+// kColsChunk / K slots of K columns each, loaded coalesced as they lie in memory. Threads
+// 0 .. K-1 carry one column's sum each through the chunks in row order (K consecutive LDS words
+// per slot: no bank conflict), first over row i and then, with -F1 in slot t's place, over row j.
+//
+// Args::kLossy: as in kp_heavy, every thread takes the same decision on m1, so the chunk loop of
+// row j, which has barriers, is skipped by all threads or by none.
+template <class Args>
+__global__ __launch_bounds__(kBlock) void kp_heavy_cols(Args A, int K) {
+  constexpr bool kLossy = Args::kLossy;
+  __shared__ double s_f[kColsChunk];
+  const int tid = threadIdx.x;
+  const int chunk = kColsChunk / K;  // slots per chunk
+  const unsigned listed = *A.n_heavy;
+  const unsigned cnt = (int64_t)listed < A.heavy_cap ? listed : (unsigned)A.heavy_cap;
+  unsigned n_lost1 = 0, n_lost2 = 0;  // kLossy: thread 0 counts this block's pairs
+  for (unsigned q = blockIdx.x; q < cnt; q += gridDim.x) {
+    const int i = A.heavy[q].x, j = A.heavy[q].y;
+    const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
+    const int64_t bj = A.rowptr[j], dj = A.rowptr[j + 1] - bj;
+    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+    const int64_t kt = A.rev[ks];
+    bool lost1 = false, lost2 = false;
+    if constexpr (kLossy) {
+      lost1 = message_lost(A, kt);
+      lost2 = message_lost(A, ks);
+    }
+    double S = 0.0;
+    for (int64_t c0 = 0; c0 < di; c0 += chunk) {
+      const int m = (int)(di - c0 < chunk ? di - c0 : chunk);
+      const double *src = A.f + (bi + c0) * K;
+      for (int e = tid; e < m * K; e += kBlock) s_f[e] = src[e];
+      __syncthreads();
+      if (tid < K)
+        for (int d = 0; d < m; ++d) S = S + s_f[d * K + tid];
+      __syncthreads();
+    }
+    double a_i = 0.0, F1 = 0.0;
+    if (tid < K) {
+      const double cs = A.c[ks * K + tid];
+      a_i = fire_avg(cs, A.v[(int64_t)i * K + tid], S);
+      F1 = (A.f[ks * K + tid] + a_i) - cs;
+    }
+    if (kLossy && lost1) {  // the same in every thread of the block
+      if (tid < K) {
+        A.f[ks * K + tid] = F1;
+        A.c[ks * K + tid] = a_i;
+        A.last[(int64_t)i * K + tid] = a_i;
+      }
+      if (tid == 0) {
+        A.fired[i] = 1;
+        n_lost1 += 1;
+      }
+      continue;
+    }
+    S = 0.0;
+    for (int64_t c0 = 0; c0 < dj; c0 += chunk) {
+      const int m = (int)(dj - c0 < chunk ? dj - c0 : chunk);
+      const double *src = A.f + (bj + c0) * K;
+      for (int e = tid; e < m * K; e += kBlock) s_f[e] = src[e];
+      __syncthreads();
+      if (tid < K) {
+        const int64_t t = kt - bj - c0;  // slot t's place in this chunk, if it is in it
+        for (int d = 0; d < m; ++d) S = S + (d == t ? -F1 : s_f[d * K + tid]);
+      }
+      __syncthreads();
+    }
+    if (tid < K) {
+      const double a_j = fire_avg(a_i, A.v[(int64_t)j * K + tid], S);
+      const double F2 = (-F1 + a_j) - a_i;
+      const bool kept = kLossy && lost2;
+      A.f[ks * K + tid] = kept ? F1 : -F2;
+      A.c[ks * K + tid] = kept ? a_i : a_j;
+      A.f[kt * K + tid] = F2;
+      A.c[kt * K + tid] = a_j;
+      A.last[(int64_t)i * K + tid] = a_i;
+      A.last[(int64_t)j * K + tid] = a_j;
+    }
+    if (tid == 0) {
+      A.fired[i] = 1;
+      A.fired[j] = 1;
+      if (kLossy && lost2) n_lost2 += 1;
+    }
+  }
+  if constexpr (kLossy) {
+    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
+    if (tid == 0 && n_lost1) atomicAdd(mine, (u64)n_lost1);
+    if (tid == 0 && n_lost2) atomicAdd(mine + 1, (u64)n_lost2);
+  }
+}
+
 // How many nodes have never fired: one atomic per block that found some.
 __global__ __launch_bounds__(kBlock) void kp_count_unfired(int n, const unsigned char *__restrict__ fired,
                                                            u64 *__restrict__ out) {
@@ -393,13 +643,25 @@ struct fu_pair : handle_base {
   uint64_t loss_seed = 0;
   bool has_mask = false;
   unsigned char *down = nullptr;  // E bytes, allocated when a mask is first set
+  bool cols = false;  // made by fu_pair_create_k: v and last hold n * width doubles, f and c E * width, and the rounds are the *_cols kernels
 };
 
 constexpr int kStats = 2 + kLostLines * kLostStride;
 
 static unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
 
-static int launch_err(fu_pair *h, u64 *slot) { return launch_max_err<kBlock>(h, h->last, slot); }
+static int launch_err(fu_pair *h, u64 *slot) {
+  if (!h->cols) return launch_max_err<kBlock>(h, h->last, slot);
+  static_assert(kBlock == kColsErrBlock, "k_max_err_cols is launched with this file's block");
+  const int K = h->width;
+  const long long total = (long long)h->n * K;
+  const int tb = (kBlock / K) * K;
+  const unsigned grid = (unsigned)std::min<long long>(1024, (total + tb - 1) / tb);
+  hipLaunchKernelGGL(k_max_err_cols, dim3(grid), dim3(kBlock), 0, h->stream, total, K, h->last, h->target,
+                     (const unsigned char *)nullptr, slot);
+  HIP_TRY(hipGetLastError());
+  return FU_OK;
+}
 
 static int launch_round(fu_pair *h) {
   RoundArgs A;
@@ -425,13 +687,25 @@ static int launch_round(fu_pair *h) {
     else
       hipLaunchKernelGGL(kp_scan, grid, block, 0, h->stream, A);
     const dim3 heavy_grid(std::min(h->n_heavy_rows, kHeavyBlocks));
-    if (h->p > 0.0 || h->has_mask) {
-      LossArgs X;
+    const bool lossy = h->p > 0.0 || h->has_mask;
+    LossArgs X;
+    if (lossy) {
       static_cast<RoundArgs &>(X) = A;
       X.down = h->has_mask ? h->down : nullptr;
       X.lost = h->stat + 2;
       X.lkey = loss_key(h->loss_seed, (uint64_t)h->round);
       X.p = h->p;
+    }
+    if (h->cols) {  // a handle of fu_pair_create_k, at every K
+      const int K = h->width;
+      if (lossy) {
+        hipLaunchKernelGGL(kp_exchange_cols<LossArgs>, grid, block, 0, h->stream, X, K);
+        if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy_cols<LossArgs>, heavy_grid, block, 0, h->stream, X, K);
+      } else {
+        hipLaunchKernelGGL(kp_exchange_cols<RoundArgs>, grid, block, 0, h->stream, A, K);
+        if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy_cols<RoundArgs>, heavy_grid, block, 0, h->stream, A, K);
+      }
+    } else if (lossy) {
       hipLaunchKernelGGL(kp_exchange<LossArgs>, grid, block, 0, h->stream, X);
       if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy<LossArgs>, heavy_grid, block, 0, h->stream, X);
     } else {  // no loss, no mask: the lossless kernels as they always ran
@@ -446,10 +720,10 @@ static int launch_round(fu_pair *h) {
 
 // Zero state: flows, caches, last averages, fired flags, counters; every word without a proposal.
 static int zero_state(fu_pair *h) {
-  const size_t e = (size_t)std::max<int64_t>(h->E, 1), n = (size_t)h->n;
-  HIP_TRY(hipMemsetAsync(h->f, 0, sizeof(double) * e, h->stream));
-  HIP_TRY(hipMemsetAsync(h->c, 0, sizeof(double) * e, h->stream));
-  HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n, h->stream));
+  const size_t e = (size_t)std::max<int64_t>(h->E, 1), n = (size_t)h->n, k = (size_t)h->width;
+  HIP_TRY(hipMemsetAsync(h->f, 0, sizeof(double) * e * k, h->stream));
+  HIP_TRY(hipMemsetAsync(h->c, 0, sizeof(double) * e * k, h->stream));
+  HIP_TRY(hipMemsetAsync(h->last, 0, sizeof(double) * n * k, h->stream));
   HIP_TRY(hipMemsetAsync(h->fired, 0, n, h->stream));
   HIP_TRY(hipMemsetAsync(h->word, 0xFF, sizeof(u64) * n, h->stream));
   HIP_TRY(hipMemsetAsync(h->stat, 0, sizeof(u64) * kStats, h->stream));
@@ -468,36 +742,69 @@ int fu_pair_destroy(fu_pair *h) {
   return FU_OK;
 }
 
-// Every check on the arguments comes before the first HIP call, so a host without a GPU
-// reports an asymmetric graph or a bad rev as such.
-int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
-                   const double *value, int32_t device, fu_pair **out) {
+}  // extern "C"
+
+// fu_pair_create (k = 1, cols = false) and fu_pair_create_k (`entry` names the one called, for
+// the messages). Every check on the arguments comes before the first HIP call, so a host without
+// a GPU reports a bad k, an asymmetric graph or a bad rev as such.
+static int pair_create(const char *entry, int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                       int32_t k, bool cols, const double *value, int32_t device, fu_pair **out) {
   FU_TRY_BEGIN
-  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_pair>("create");
+  if (!out || !rowptr || !value || n <= 0 || e < 0 || (e > 0 && !col)) return bad_arguments<fu_pair>(entry);
+  const std::string who = std::string("fu_pair_") + entry;
+  if (k < 1 || k > kMaxCols) return fail(FU_ERR_ARG, who + ": k must be in 1..16, got " + std::to_string(k));
   std::vector<int32_t> built;
-  if (int rc = pairing_rev("fu_pair_create", n, e, rowptr, col, &rev, &built)) return rc;
+  if (int rc = pairing_rev(who, n, e, rowptr, col, &rev, &built)) return rc;
   int32_t heavy_rows = 0;
   for (int32_t i = 0; i < n; ++i) heavy_rows += rowptr[i + 1] - rowptr[i] > kLightDeg;
   auto *h = new fu_pair();
   h->n_heavy_rows = heavy_rows;
+  h->cols = cols;
   auto cleanup = [&](int code) { fu_pair_destroy(h); return code; };
   int rc = FU_OK;
-  if ((rc = handle_open(h, device, n, e, 1))) return cleanup(rc);
+  if ((rc = handle_open(h, device, n, e, k))) return cleanup(rc);
+  const int64_t nk = (int64_t)n * k, ek = std::max<int64_t>(e, 1) * k;
   if ((rc = dmalloc(h, &h->rowptr, (int64_t)n + 1)) || (rc = dmalloc(h, &h->col, e)) || (rc = dmalloc(h, &h->rev, e)) ||
-      (rc = dmalloc(h, &h->v, n)) || (rc = dmalloc(h, &h->f, e)) || (rc = dmalloc(h, &h->c, e)) ||
-      (rc = dmalloc(h, &h->last, n)) || (rc = dmalloc(h, &h->word, n)) || (rc = dmalloc(h, &h->fired, n)) ||
+      (rc = dmalloc(h, &h->v, nk)) || (rc = dmalloc(h, &h->f, ek)) || (rc = dmalloc(h, &h->c, ek)) ||
+      (rc = dmalloc(h, &h->last, nk)) || (rc = dmalloc(h, &h->word, n)) || (rc = dmalloc(h, &h->fired, n)) ||
       (rc = dmalloc(h, &h->heavy, heavy_rows)) || (rc = dmalloc(h, &h->n_heavy, 1)) || (rc = dmalloc(h, &h->stat, kStats)))
     return cleanup(rc);
   if ((rc = put(h, h->rowptr, rowptr, (int64_t)n + 1)) || (rc = put(h, h->col, col, e)) || (rc = put(h, h->rev, rev, e)) ||
-      (rc = put(h, h->v, value, n)) || (rc = zero_state(h)))
+      (rc = put(h, h->v, value, nk)) || (rc = zero_state(h)))
     return cleanup(rc);
   *out = h;
   return FU_OK;
   FU_TRY_END
 }
 
+extern "C" {
+
+int fu_pair_create(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev,
+                   const double *value, int32_t device, fu_pair **out) {
+  return pair_create("create", n, e, rowptr, col, rev, 1, /*cols=*/false, value, device, out);
+}
+
+int fu_pair_create_k(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col, const int32_t *rev, int32_t k,
+                     const double *value, int32_t device, fu_pair **out) {
+  return pair_create("create_k", n, e, rowptr, col, rev, k, /*cols=*/true, value, device, out);
+}
+
 int fu_pair_create_from_graph(const fu_graph *g, const double *value, int32_t device, fu_pair **out) {
   return create_from_graph<fu_pair>(g, value, out, [&](auto... csr) { return fu_pair_create(csr..., value, device, out); });
+}
+
+int fu_pair_create_from_graph_k(const fu_graph *g, int32_t k, const double *value, int32_t device, fu_pair **out) {
+  FU_TRY_BEGIN
+  if (g && value && out && (k < 1 || k > kMaxCols))  // after the null checks, before the graph's
+    return fail(FU_ERR_ARG, "fu_pair_create_from_graph_k: k must be in 1..16, got " + std::to_string(k));
+  return create_from_graph<fu_pair>(g, value, out, [&](auto... csr) { return fu_pair_create_k(csr..., k, value, device, out); });
+  FU_TRY_END
+}
+
+int fu_pair_get_columns(fu_pair *h, int32_t *k) {
+  if (!h || !k) return bad_arguments<fu_pair>("get_columns");
+  *k = h->width;
+  return FU_OK;
 }
 
 int fu_pair_set_seed(fu_pair *h, uint64_t seed) {
@@ -542,7 +849,7 @@ int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
 
 int fu_pair_set_values(fu_pair *h, const double *value) {
   if (!h || !value) return bad_arguments<fu_pair>("set_values");
-  return upload(h, h->v, value, sizeof(double) * (size_t)h->n);
+  return upload(h, h->v, value, sizeof(double) * (size_t)h->n * h->width);
 }
 
 int fu_pair_reset(fu_pair *h) {
@@ -562,17 +869,17 @@ int fu_pair_synchronize(fu_pair *h) { return synchronize(h); }
 // The state is on the device from create on: round 0 downloads like any other.
 int fu_pair_get_estimates(fu_pair *h, double *last_out) {
   if (!h || !last_out) return bad_arguments<fu_pair>("get_estimates");
-  return download(h, last_out, h->last, sizeof(double) * (size_t)h->n);
+  return download(h, last_out, h->last, sizeof(double) * (size_t)h->n * h->width);
 }
 
 int fu_pair_get_flows(fu_pair *h, double *f_out) {
   if (!h || (!f_out && h->E)) return bad_arguments<fu_pair>("get_flows");
-  return download(h, f_out, h->f, sizeof(double) * (size_t)h->E);
+  return download(h, f_out, h->f, sizeof(double) * (size_t)h->E * h->width);
 }
 
 int fu_pair_get_cache(fu_pair *h, double *c_out) {
   if (!h || (!c_out && h->E)) return bad_arguments<fu_pair>("get_cache");
-  return download(h, c_out, h->c, sizeof(double) * (size_t)h->E);
+  return download(h, c_out, h->c, sizeof(double) * (size_t)h->E * h->width);
 }
 
 int fu_pair_get_stats(fu_pair *h, int64_t out[2]) {

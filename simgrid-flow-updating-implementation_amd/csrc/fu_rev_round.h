@@ -33,6 +33,7 @@
 // get_estimates and get_flows. Everything has internal linkage.
 #pragma once
 
+#include "fu_cols_err.h"
 #include "fu_handle.h"
 
 namespace fu {
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void k_heavy(RoundArgs A, typename R::Args 
 // contiguous read spread over K adjacent lanes. Between the two, a slot's kind sits in s_kind[q]
 // and its two gather indices in the first element of its own LDS rows (s_F[q * K], s_E[q * K],
 // as bit patterns): no LDS beyond the scalar kernels' 34 KB.
-constexpr int kMaxCols = 16;
+static_assert(kBlock == kColsErrBlock, "k_max_err_cols (fu_handle.h) is launched with this file's block");
 static_assert(kChunk == kTileEdges, "stash_slots and load_elems serve both kernels");
 static_assert(kHeavyDeg * kMaxCols <= kTileEdges, "a light row alone fits a tile at every K");
 
@@ -419,32 +420,6 @@ __global__ __launch_bounds__(kBlock) void k_heavy_cols(RoundArgs A, typename R::
     });
   }
   R::block_end(X, own_slots);
-}
-
-// max |a - target| per column as uint64 bit patterns, the rule of the scaffold's k_max_err for
-// a_old = x[i * K + c]: a NaN raises its own column's slot and no other. With `alive`, over the
-// alive nodes only. Each thread keeps one column: a block uses (kBlock / K) * K threads and the
-// stride is a multiple of K.
-__global__ __launch_bounds__(kBlock) void k_max_err_cols(i64 total, int K, const double *__restrict__ a,
-                                                         const double *__restrict__ target,
-                                                         const unsigned char *__restrict__ alive, u64 *__restrict__ err) {
-  __shared__ u64 s_m[kMaxCols];
-  const int tb = (kBlock / K) * K;
-  const int tid = threadIdx.x;
-  if (tid < kMaxCols) s_m[tid] = 0ull;
-  __syncthreads();
-  if (tid < tb) {
-    u64 m = 0ull;
-    const i64 stride = (i64)gridDim.x * tb;
-    for (i64 q = (i64)blockIdx.x * tb + tid; q < total; q += stride) {
-      if (alive != nullptr && !alive[q / K]) continue;
-      const u64 x = (u64)__double_as_longlong(fabs(a[q] - target[q]));
-      m = x > m ? x : m;
-    }
-    if (m) atomicMax(&s_m[tid % K], m);
-  }
-  __syncthreads();
-  if (tid < K && s_m[tid]) atomicMax(&err[tid], s_m[tid]);
 }
 
 // ---- the handle -----------------------------------------------------------------------------

@@ -7,6 +7,7 @@
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --loss 0.1 [--loss-seed 7]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --pair-columns 4 [--loss 0.1]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 [--churn-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 --columns 4   # or --loss
 
@@ -22,7 +23,7 @@ import time
 import numpy as np
 
 from .engine import (CollectAll, CollectAllChurn, CollectAllChurnBatch, CollectAllLossy, CollectAllLossyBatch, PairwiseSync,
-                     churn_targets)
+                     PairwiseSyncBatch,                      churn_targets)
 from .graph import Graph, component_means, uniform_values
 from .sim import CollectAllPeer, Engine, run_reference_main
 
@@ -66,7 +67,14 @@ def main(argv=None):
     ap.add_argument("--churn-seed", type=int, default=0)
     ap.add_argument("--columns", type=int, default=None,
                     help="bench-graph with --loss or --churn: K value columns in one handle (1..16)")
+    ap.add_argument("--pair-columns", type=int, default=None,
+                    help="bench-graph with --pairs: K value columns over one matching (1..16)")
     a = ap.parse_args(argv)
+    if a.pair_columns is not None:
+        if a.mode != "bench-graph" or not a.pairs:
+            ap.error("--pair-columns needs bench-graph with --pairs")
+        if not 1 <= a.pair_columns <= 16:
+            ap.error("--pair-columns must be in 1..16")
     if a.columns is not None:
         if a.mode != "bench-graph" or (a.loss is None and a.churn is None):
             ap.error("--columns needs bench-graph with --loss or --churn")
@@ -98,19 +106,27 @@ def main(argv=None):
         if a.columns is not None:
             ap.error("--columns needs --loss or --churn without --pairs")
         g = Graph.from_spec(a.spec, seed=a.seed)
-        v = uniform_values(g.n, seed=0)
-        eng = PairwiseSync(g, v, seed=a.pair_seed, device=a.device)
+        if a.pair_columns is None:
+            v = uniform_values(g.n, seed=0)
+            eng = PairwiseSync(g, v, seed=a.pair_seed, device=a.device)
+        else:
+            v = _columns(g.n, a.pair_columns)
+            eng = PairwiseSyncBatch(g, v, seed=a.pair_seed, device=a.device)
         if a.loss is not None:
             eng.set_loss(a.loss, a.loss_seed)
         t0 = time.perf_counter()
         ms = eng.run_timed(a.rounds)
         wall = time.perf_counter() - t0
-        tgt, _ = component_means(g.rowptr, g.col, v)
+        if a.pair_columns is None:
+            tgt, _ = component_means(g.rowptr, g.col, v)
+        else:
+            tgt = churn_targets(g, v)  # everything alive: component_means per column
         eng.set_targets(tgt)
         print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
               f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
-              f"max_err={eng.max_err():.3e} pairs={eng.stats[0]}"
-              + ("" if a.loss is None else f" lost={sum(eng.loss_stats[:2])}"))
+              f"max_err={np.max(eng.max_err()):.3e} pairs={eng.stats[0]}"
+              + ("" if a.loss is None else f" lost={sum(eng.loss_stats[:2])}")
+              + ("" if a.pair_columns is None else f" columns={a.pair_columns}"))
         return 0
     if a.mode == "bench-graph" and a.loss is not None:
         g = Graph.from_spec(a.spec, seed=a.seed)

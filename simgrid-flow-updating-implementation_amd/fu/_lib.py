@@ -132,6 +132,9 @@ _SIGS = {
     "fu_churn_live": ([i32, vp, vp, vp, vp, vp, vp], ctypes.c_int),
     "fu_pair_create": ([i32, i64, vp, vp, vp, vp, i32, P(vp)], ctypes.c_int),
     "fu_pair_create_from_graph": ([vp, vp, i32, P(vp)], ctypes.c_int),
+    "fu_pair_create_k": ([i32, i64, vp, vp, vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_pair_create_from_graph_k": ([vp, i32, vp, i32, P(vp)], ctypes.c_int),
+    "fu_pair_get_columns": ([vp, P(i32)], ctypes.c_int),
     "fu_pair_set_seed": ([vp, u64], ctypes.c_int),
     "fu_pair_set_option": ([vp, cp, i64], ctypes.c_int),
     "fu_pair_set_values": ([vp, vp], ctypes.c_int),

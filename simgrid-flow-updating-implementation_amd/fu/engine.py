@@ -16,6 +16,8 @@
   slot, K-wide contiguous gathers; each column bit-equal to a run of the scalar class.
 * `PairwiseSync`: synchronous pairwise rounds (fu_pair_*): a matching per round chosen on the
   device, one full pairwise exchange per matched pair; `pair_matching` restates it on the host.
+* `PairwiseSyncBatch`: K value columns over one matching (fu_pair_create_k): one pointer chain,
+  one loss decision and K contiguous flows per pair; each column bit-equal to a `PairwiseSync`.
 * `Trace` + `Replay`: the tick-level schedule of the reference run (Peer.loop, CA:70-85 /
   PW:69-84, and the SimGrid mailboxes), built natively on the host and replayed on the
   GPU one tick per batch. Used by the pairwise mode and by faithful small-platform runs.
@@ -543,6 +545,9 @@ class PairwiseSync(_Handle):
     def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
                  seed: int = 0, loss: float = 0.0, loss_seed: int = 0, link_mask=None, device: int = 0):
         self._open(graph, values, rowptr, col, rev, device)
+        self._configure(seed, loss, loss_seed, link_mask)
+
+    def _configure(self, seed, loss, loss_seed, link_mask):
         if seed != 0:
             self.set_seed(seed)
         try:
@@ -582,7 +587,7 @@ class PairwiseSync(_Handle):
 
     def cache(self) -> np.ndarray:
         """The cached estimate of every slot."""
-        c = np.empty(max(self.E, 1))
+        c = np.empty(self._shape(max(self.E, 1)))
         L.call("fu_pair_get_cache", self._h, L.ptr(c))
         return c[:self.E]
 
@@ -598,6 +603,30 @@ class PairwiseSync(_Handle):
         s = np.zeros(3, dtype=np.int64)
         L.call("fu_pair_get_loss_stats", self._h, L.ptr(s))
         return int(s[0]), int(s[1]), int(s[2])
+
+
+class PairwiseSyncBatch(PairwiseSync):
+    """K value columns over one matching (fu_pair_create_k): `values` has shape (n, K),
+    1 <= K <= 16. One message carries all K (flow, estimate) pairs, so the matching of a round,
+    the loss outcomes of a pair, the link mask, `stats` and `loss_stats` are those of one
+    `PairwiseSync` with the same seeds; column c is a `PairwiseSync` run of column c, bit for bit.
+    estimates, targets and values are (n, K), flows and cache (E, K), the error trace
+    (checks, K), max_err (K,).
+
+    >>> one = np.zeros(g.n); one[0] = 1.0
+    >>> eng = PairwiseSyncBatch(g, np.stack([x, one], axis=1), seed=7); eng.run(2000)
+    >>> avg, inv_n = eng.estimates()[5]; count, total = 1 / inv_n, avg / inv_n
+    """
+
+    _C = _c_names("fu_pair_", create="fu_pair_create_k", create_from_graph="fu_pair_create_from_graph_k")
+    _NDIM = 2
+    _ROWS = "values.shape[0]"
+
+    def __init__(self, graph: Graph | None = None, values=None, *, rowptr=None, col=None, rev=None,
+                 seed: int = 0, loss: float = 0.0, loss_seed: int = 0, link_mask=None, device: int = 0):
+        self._open(graph, values, rowptr, col, rev, device, extra=_columns)
+        self.K = self._cols = int(self.values.shape[1])
+        self._configure(seed, loss, loss_seed, link_mask)
 
 
 class Trace:

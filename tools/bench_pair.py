@@ -25,7 +25,18 @@
    (a lost m1 skips row j, v_j and c[t] and three of the six stores; a lost m2 moves the same
    bytes as a complete exchange; the mask-free decision reads nothing).
 
+4. With --columns K [K ...]: in place of 2, the same two graphs and windows for one scalar handle
+   (fu.PairwiseSync) and one fu.PairwiseSyncBatch per K, all on the "atomic_min" matching and
+   without loss; the handles alternate within each repetition. Column 0 of every K-column handle
+   is compared bit for bit with the scalar handle before any number is printed. One JSON line
+   per graph and handle with us_per_round (median, min, max), k_scalar_us = K times the scalar
+   handle's median of the same session, ratio = us_per_round / k_scalar_us, and the byte model
+     bytes = sum over pairs of K (8 (deg_i + deg_j) + 80) + 36
+   (per column both flow rows, c[s], c[t], v_i, v_j and the six stores; per pair four row
+   pointers and one rev).
+
     python tools/bench_pair.py [--rounds 200] [--n 1000000] [--reps 7] [--skip-replay] [--loss 0.1 0.3]
+    python tools/bench_pair.py --skip-replay --columns 1 2 4 8 16
 """
 import argparse
 import ctypes
@@ -242,6 +253,61 @@ def big_lossy(name, g, rounds, reps, copy_gbs, losses):
             eng.close()
 
 
+def columns_values(n, K):
+    """(n, K): column 0 the scalar run's inputs, column 1 the COUNT indicator, then uniform streams."""
+    cols = [fu.uniform_values(n, seed=0)]
+    if K > 1:
+        one = np.zeros(n)
+        one[0] = 1.0
+        cols.append(one)
+    cols += [fu.uniform_values(n, seed=c) for c in range(2, K)]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+def big_columns(name, g, rounds, reps, copy_gbs, widths):
+    """us per round of the scalar handle and of a K-column handle per K of `widths`, the handles
+    alternating within each repetition."""
+    per_pair_1 = model_bytes_per_pair(g, SEED)  # 8 (deg_i + deg_j) + 116
+    engs = [fu.PairwiseSync(g, fu.uniform_values(g.n, seed=0), seed=SEED)]
+    engs += [fu.PairwiseSyncBatch(g, columns_values(g.n, K), seed=SEED) for K in widths]
+    try:
+        for eng in engs:
+            eng.run(rounds)  # warm
+        t = [[] for _ in engs]
+        pairs = 0
+        for _ in range(reps):
+            for q, eng in enumerate(engs):
+                eng.reset()
+                eng.run(1)
+                eng.synchronize()
+                first = eng.stats[0]
+                t[q].append(eng.run_timed(rounds - 1) * 1e3 / (rounds - 1))
+                pairs = eng.stats[0] - first
+        ref = (engs[0].estimates(), engs[0].flows(), engs[0].cache())
+        for eng in engs[1:]:
+            state = (eng.estimates()[:, 0], eng.flows()[:, 0], eng.cache()[:, 0])
+            if not all(same_bits(np.ascontiguousarray(a), b) for a, b in zip(state, ref)):
+                raise SystemExit("bench_pair: column 0 of a K-column handle differs from the scalar handle")
+        ppr = pairs / (rounds - 1)
+        scalar_us = statistics.median(t[0])
+        for q, (eng, K) in enumerate(zip(engs, [None] + list(widths))):
+            us = statistics.median(t[q])
+            k = K or 1
+            per_pair = k * (per_pair_1 - 36) + 36
+            line = {"graph": name, "n": g.n, "E": g.E, "handle": "scalar" if K is None else "columns", "columns": k,
+                    "rounds_timed": [1, rounds - 1], "reps": reps, "us_per_round": round(us, 2),
+                    "us_per_round_min": round(min(t[q]), 2), "us_per_round_max": round(max(t[q]), 2),
+                    "pairs_per_round": round(ppr, 1), "model_bytes_per_pair": round(per_pair, 1),
+                    "model_bytes_per_round": int(ppr * per_pair), "roofline": round(ppr * per_pair / PEAK / (us * 1e-6), 5),
+                    "copy_GBs": copy_gbs}
+            if K is not None:
+                line.update({"k_scalar_us": round(k * scalar_us, 2), "ratio_over_k_scalar": round(us / (k * scalar_us), 4)})
+            print(json.dumps(line), flush=True)
+    finally:
+        for eng in engs:
+            eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
@@ -250,12 +316,20 @@ def main():
     ap.add_argument("--skip-replay", action="store_true")
     ap.add_argument("--loss", type=float, nargs="+", default=None, metavar="P",
                     help="time the big graphs at p = 0 and at every P, in place of the A/B of the matching")
+    ap.add_argument("--columns", type=int, nargs="+", default=None, metavar="K",
+                    help="time the big graphs with a scalar handle and a K-column handle per K, in place of the A/B of the matching")
     a = ap.parse_args()
+    if a.columns is not None and (a.loss is not None or not all(1 <= k <= 16 for k in a.columns)):
+        ap.error("--columns takes widths in 1..16 and does not combine with --loss")
     if a.rounds < 2:
         ap.error("--rounds must be at least 2 (round 0 is not timed)")
     if not a.skip_replay:
         against_replay(a.rounds)
     copy_gbs = round(fu.copy_bandwidth(0), 1)
+    if a.columns is not None:
+        big_columns(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs, a.columns)
+        big_columns(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs, a.columns)
+        return
     if a.loss is not None:
         if not all(0.0 <= p <= 1.0 for p in a.loss):
             ap.error("--loss takes probabilities in [0, 1]")
