@@ -1,6 +1,6 @@
-// The per-column error reduction of the K-column handles: included by fu_rev_round.h (the
-// rev-gather round of fu_lossy.hip and fu_churn.hip at K columns) and by fu_pair.hip
-// (fu_pair_create_k). It sits on csrc/fu_handle.h. DESIGN.md §4.19, §4.22.
+// The per-column error reduction of the K-column handles, kernel and launch: included by
+// fu_rev_round.h (the rev-gather round of fu_lossy.hip and fu_churn.hip at K columns) and by
+// fu_pair.hip (fu_pair_create_k). It sits on csrc/fu_handle.h. DESIGN.md §4.19, §4.22.
 #pragma once
 
 #include "fu_handle.h"
@@ -42,9 +42,19 @@ __global__ __launch_bounds__(kBlock) void k_max_err_cols(i64 total, int K, const
   __syncthreads();
   if (tid < K && s_m[tid]) atomicMax(&err[tid], s_m[tid]);
 }
+
+// launch_err of a handle of K = h->width columns: a holds n * K doubles, alive may be null, the
+// K maxima go to slot[0 .. K-1]. The kernel's block is its own, whatever the includer's is.
+inline int launch(const handle_base *h, const double *a, const unsigned char *alive, u64 *slot) {
+  const int K = h->width;
+  const i64 total = (i64)h->n * K;
+  const int tb = (kBlock / K) * K;
+  const unsigned grid = (unsigned)std::min<i64>(1024, (total + tb - 1) / tb);
+  hipLaunchKernelGGL(k_max_err_cols, dim3(grid), dim3(kBlock), 0, h->stream, total, K, a, h->target, alive, slot);
+  HIP_TRY(hipGetLastError());
+  return FU_OK;
+}
 }  // namespace cols_err
-using cols_err::k_max_err_cols;
-constexpr int kColsErrBlock = cols_err::kBlock;
 
 }  // namespace
 }  // namespace fu

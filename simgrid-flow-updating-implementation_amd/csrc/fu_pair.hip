@@ -39,20 +39,28 @@
 // A round is kp_propose (one 64-bit atomicMin per valid proposal into the listener's word) or
 // kp_scan (every listener hashes its own row; no atomics), then kp_exchange (a block compacts
 // its matched listeners, 8 lanes per pair load both flow rows into LDS, one lane carries the
-// two chains), then kp_heavy for the pairs with a row above kLightDeg (one block per pair, the
-// rows in LDS chunks, thread 0 carrying). Nothing in a round waits for the host.
+// two chains), then kp_heavy<Args, true> for the pairs with a row above kLightDeg (one block per
+// pair, the rows in LDS chunks, thread 0 carrying). Nothing in a round waits for the host.
 //
 // A handle of K value columns (fu_pair_create_k) keeps v and last node-major
 // (x[i * K + c]) and f and c edge-major (f[k * K + c]). The matching, the loss decisions, the
 // heavy list, `fired` and the counters are per handle, as for one column; column c follows the
 // exchange above on its own and no arithmetic crosses columns. Such a handle runs kp_propose or
 // kp_scan as they are, then kp_exchange_cols (lane l of a pair's group carries columns l and
-// l + 8 and reads its rows straight from memory) and kp_heavy_cols (threads 0 .. K-1 carry a
-// column each through chunks of kColsChunk / K slots).
+// l + 8 and reads its rows straight from memory) and kp_heavy<Args, false> (threads 0 .. K-1
+// carry a column each through chunks of kColsChunk / K slots).
+//
+// What the kernels share is stated once: compact_matched (a block's words consumed, its pairs
+// in listener order), `fire` (the arithmetic of steps 1 and 2), fired_unheard and settle (what
+// each of the three outcomes writes into one column's cells: kp_exchange_cols and kp_heavy call
+// them, kp_exchange writes its one column out itself, for a measured reason given there),
+// list_heavy and the two flushes of the lost-message counters. The two exchange kernels differ
+// on purpose; the heavy kernel is one body in two instantiations.
 //
 // The handle scaffold (create and destroy, the run loops, the error slots and k_max_err, the
 // small entry points) is csrc/fu_handle.h, shared with the batched and lossy engines; the
-// per-column error reduction k_max_err_cols is csrc/fu_cols_err.h, shared with the rev-gather round.
+// per-column error reduction, kernel and launch, is csrc/fu_cols_err.h, shared with the
+// rev-gather round.
 #include "fu_cols_err.h"
 #include "fu_handle.h"
 
@@ -64,9 +72,9 @@ constexpr int kBlock = 256;                 // threads per block (4 waves of 64)
 constexpr int kGroup = 8;                   // kp_exchange: lanes that load one pair's rows
 constexpr int kGroups = kBlock / kGroup;    // pairs a block works on at once
 constexpr int kLightDeg = 64;               // a pair with a row above this degree goes to kp_heavy
-constexpr int kChunk = 1024;                // kp_heavy: flows staged in LDS per chunk
+constexpr int kChunk = 1024;                // kp_heavy<Args, true>: flows staged in LDS per chunk
 constexpr int kHeavyBlocks = 1024;          // kp_heavy: at most this many blocks share the round's heavy pairs
-constexpr int kColsChunk = 2048;            // kp_heavy_cols: doubles staged in LDS per chunk, kColsChunk / K slots
+constexpr int kColsChunk = 2048;            // kp_heavy<Args, false>: doubles staged in LDS per chunk, kColsChunk / K slots
 constexpr int kColsBatch = 8;               // kp_exchange_cols: a lane's loads of one column in flight before the adds
 static_assert(kMaxCols <= 2 * kGroup, "a lane of a group carries at most two columns");
 static_assert(kColsChunk / kMaxCols >= 1, "a chunk holds a slot at every K");
@@ -114,13 +122,8 @@ struct RoundArgs {
   static constexpr bool kLossy = false;
 };
 
-// One fire and the answer to it, from the two sums: what the pair writes back.
-struct Exchange {
-  double a_i, a_j, F2;
-};
-
-// The arguments of the lossy forms of the exchange kernels: kp_exchange<LossArgs> and
-// kp_heavy<LossArgs>. The lossless handle runs kp_exchange<RoundArgs> and kp_heavy<RoundArgs>.
+// The arguments of the lossy instantiations of kp_exchange, kp_exchange_cols and kp_heavy; a
+// handle without loss or mask runs the <RoundArgs> ones.
 struct LossArgs : RoundArgs {
   const unsigned char *down;  // per slot: non-zero loses every message received on it; may be null
   u64 *lost;                  // the handle's counter pairs: [q * kLostStride] first messages lost, [.. + 1] answers lost
@@ -139,6 +142,55 @@ __device__ inline bool message_lost(const LossArgs &X, int64_t k) {
 }
 
 __device__ inline double fire_avg(double c, double v, double S) { return (c + (v - S)) / 2.0; }
+
+// ---- one pair, one column: the arithmetic and the three outcomes ------------------------------
+// A node of value v whose row sums to S fires on a slot holding flow f and cache c: its new
+// average a and the flow F it sends. Step 1 is fire(f[ks], c[ks], v_i, S_i, a_i, F1); step 2,
+// after j has received (c[kt] = a_i, f[kt] = -F1, the latter already in S_j), is
+// fire(-F1, a_i, v_j, S_j, a_j, F2), so F2 = (-F1 + a_j) - a_i.
+__device__ inline void fire(double f, double c, double v, double S, double &a, double &F) {
+  a = fire_avg(c, v, S);
+  F = (f + a) - c;
+}
+
+// What a pair leaves in one column's cells: fs, cs = f, c at ks; ft, ct = f, c at kt; li, lj =
+// last at i, j. `fired` and the counters are per pair and stay with the caller.
+// m1 lost: i fired into a message nobody received; row j is not touched.
+__device__ inline void fired_unheard(double *fs, double *cs, double *li, double F1, double a_i) {
+  *fs = F1;
+  *cs = a_i;
+  *li = a_i;
+}
+// m1 received. kept: m2 lost, j answered and i never heard it, so i keeps what it fired;
+// otherwise delivered, the lossless exchange.
+__device__ inline void settle(double *fs, double *cs, double *ft, double *ct, double *li, double *lj, double a_i,
+                              double a_j, double F1, double F2, bool kept) {
+  *fs = kept ? F1 : -F2;
+  *cs = kept ? a_i : a_j;
+  *ft = F2;
+  *ct = a_j;
+  *li = a_i;
+  *lj = a_j;
+}
+
+// A pair with a row above kLightDeg goes on the round's list for kp_heavy: one lane per pair.
+__device__ inline void list_heavy(const RoundArgs &A, int i, int j) {
+  const unsigned slot = atomicAdd(A.n_heavy, 1u);
+  if ((int64_t)slot < A.heavy_cap) A.heavy[slot] = make_int2(i, j);  // always: a heavy row is in one pair
+}
+
+// The lost-message counters of a block, into its line. The exchange kernels count per thread
+// (every thread calls this: one atomic per block and counter), kp_heavy in thread 0 alone.
+__device__ inline u64 *lost_line(const LossArgs &X) { return X.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride; }
+__device__ inline void flush_lost_block(const LossArgs &X, int n_lost1, int n_lost2) {
+  block_count_to<kBlock>(n_lost1, lost_line(X));
+  __syncthreads();  // block_count_to's LDS words are read by thread 0 until here
+  block_count_to<kBlock>(n_lost2, lost_line(X) + 1);
+}
+__device__ inline void flush_lost_thread0(const LossArgs &X, unsigned n_lost1, unsigned n_lost2) {
+  if (threadIdx.x == 0 && n_lost1) atomicAdd(lost_line(X), (u64)n_lost1);
+  if (threadIdx.x == 0 && n_lost2) atomicAdd(lost_line(X) + 1, (u64)n_lost2);
+}
 
 // ---- matching, form A: proposers push -----------------------------------------------------
 __global__ __launch_bounds__(kBlock) void kp_propose(RoundArgs A) {
@@ -168,20 +220,11 @@ __global__ __launch_bounds__(kBlock) void kp_scan(RoundArgs A) {
 // ---- the exchange ------------------------------------------------------------------------
 // Thread t of block b looks at node b * kBlock + t: a listener whose word holds a key is
 // matched with the key's low half, and writes the word back to kNone. The block compacts its
-// pairs (ballot, listener order) and works on kGroups of them at a time: the 8 lanes of a
-// group load the pair's two flow rows coalesced into the group's LDS rows, then lane 0 runs
-// both chains from LDS in row order.
-//
-// Args::kLossy: all 8 lanes of a group read rev[ks] (one address: a broadcast) and with it hold both
-// decisions of the pair, so a group whose m1 is lost never loads row j. The barriers of the q0
-// loop stay outside every per-pair branch. The lost messages are counted per thread and added
-// with one atomic per block and counter.
-template <class Args>
-__global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
-  constexpr bool kLossy = Args::kLossy;
-  __shared__ int2 s_pair[kBlock];
+// pairs (ballot, listener order) into s_pair[0 .. np-1] as (i, j); np is returned, the same in
+// every thread. Every thread of the block calls it: both barriers are in here, and s_pair is
+// complete on return.
+__device__ inline int compact_matched(const RoundArgs &A, int2 *s_pair) {
   __shared__ int s_cnt[kBlock / 64];
-  __shared__ double s_f[kGroups][2 * kLightDeg];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t node = (int64_t)blockIdx.x * kBlock + tid;
   u64 word = kNone;
@@ -200,8 +243,25 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
   }
   if (matched) s_pair[base + __popcll(bal & ((1ull << lane) - 1))] = make_int2((int)(uint32_t)word, (int)node);
   __syncthreads();
-  const int g = tid / kGroup, l = tid % kGroup;
-  int n_lost1 = 0, n_lost2 = 0;  // kLossy: this thread's pairs (lane 0 of a group counts)
+  return np;
+}
+
+// One column. The block works on kGroups of its pairs at a time: the 8 lanes of a group load
+// the pair's two flow rows coalesced into the group's LDS rows, then lane 0 runs both chains
+// from LDS in row order.
+//
+// Args::kLossy: all 8 lanes of a group read rev[ks] (one address: a broadcast) and with it hold both
+// decisions of the pair, so a group whose m1 is lost never loads row j; without loss only lane 0
+// reads it. The barriers of the q0 loop stay outside every per-pair branch. The lost messages
+// are counted per thread (lane 0 of a group counts).
+template <class Args>
+__global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
+  constexpr bool kLossy = Args::kLossy;
+  __shared__ int2 s_pair[kBlock];
+  __shared__ double s_f[kGroups][2 * kLightDeg];
+  const int np = compact_matched(A, s_pair);
+  const int tid = threadIdx.x, g = tid / kGroup, l = tid % kGroup;
+  int n_lost1 = 0, n_lost2 = 0;
   for (int q0 = 0; q0 < np; q0 += kGroups) {  // np is the same in every thread: the barriers are uniform
     const int q = q0 + g;
     bool light = false, lost1 = false, lost2 = false;
@@ -216,10 +276,7 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
       bj = A.rowptr[j];
       dj = (int)(A.rowptr[j + 1] - bj);
       if (di > kLightDeg || dj > kLightDeg) {
-        if (l == 0) {
-          const unsigned slot = atomicAdd(A.n_heavy, 1u);
-          if ((int64_t)slot < A.heavy_cap) A.heavy[slot] = make_int2(i, j);  // always: a heavy row is in one pair
-        }
+        if (l == 0) list_heavy(A, i, j);
       } else {
         light = true;
         ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
@@ -250,10 +307,12 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
     __syncthreads();
     if (light && l == 0) {
       const double *fi = s_f[g], *fj = s_f[g] + kLightDeg;
-      double S = 0.0;
+      double S = 0.0, a_i, F1;
       for (int d = 0; d < di; ++d) S = S + fi[d];
-      const double a_i = fire_avg(cs, vi, S);
-      const double F1 = (fi[ks - bi] + a_i) - cs;
+      fire(fi[ks - bi], cs, vi, S, a_i, F1);
+      // The three outcomes are written out here, not through fired_unheard and settle: with the
+      // helpers the compiler forms all six addresses before the first store, and that order
+      // measured 0.1-0.9 us a round slower on RR-1M (MEASUREMENTS.md §19.2, §19.3).
       if (kLossy && lost1) {  // i fired into a message nobody received
         A.f[ks] = F1;
         A.c[ks] = a_i;
@@ -263,8 +322,8 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
       } else {
         S = 0.0;
         for (int d = 0; d < dj; ++d) S = S + (d == t ? -F1 : fj[d]);
-        const double a_j = fire_avg(a_i, vj, S);
-        const double F2 = (-F1 + a_j) - a_i;
+        double a_j, F2;
+        fire(-F1, a_i, vj, S, a_j, F2);
         if (kLossy && lost2) {  // j answered, i never heard it
           A.f[ks] = F1;
           A.c[ks] = a_i;
@@ -284,100 +343,7 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
     __syncthreads();
   }
   if (tid == 0 && np > 0) atomicAdd(A.pairs, (u64)np);
-  if constexpr (kLossy) {
-    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
-    block_count_to<kBlock>(n_lost1, mine);
-    __syncthreads();  // block_count_to's LDS words are read by thread 0 until here
-    block_count_to<kBlock>(n_lost2, mine + 1);
-  }
-}
-
-// Pairs with a row above kLightDeg: one block per pair, at most kHeavyBlocks blocks sharing the
-// list. All threads load a chunk of a row coalesced into LDS; thread 0 carries the sum through
-// the chunk in row order, from chunk to chunk, first over row i and then, with -F1 in slot t's
-// place, over row j.
-//
-// Args::kLossy: every thread holds kt and the loss key, so every thread of the block takes the same
-// decision on m1 and the chunk loop of row j, which has barriers, is skipped by all or by none.
-template <class Args>
-__global__ __launch_bounds__(kBlock) void kp_heavy(Args A) {
-  constexpr bool kLossy = Args::kLossy;
-  __shared__ double s_f[kChunk];
-  const int tid = threadIdx.x;
-  const unsigned listed = *A.n_heavy;
-  const unsigned cnt = (int64_t)listed < A.heavy_cap ? listed : (unsigned)A.heavy_cap;
-  unsigned n_lost1 = 0, n_lost2 = 0;  // kLossy: thread 0 counts this block's pairs
-  for (unsigned q = blockIdx.x; q < cnt; q += gridDim.x) {
-    const int i = A.heavy[q].x, j = A.heavy[q].y;
-    const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
-    const int64_t bj = A.rowptr[j], dj = A.rowptr[j + 1] - bj;
-    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
-    const int64_t kt = A.rev[ks];
-    bool lost1 = false, lost2 = false;
-    if constexpr (kLossy) {
-      lost1 = message_lost(A, kt);
-      lost2 = message_lost(A, ks);
-    }
-    double S = 0.0;
-    for (int64_t c0 = 0; c0 < di; c0 += kChunk) {
-      const int m = (int)(di - c0 < kChunk ? di - c0 : kChunk);
-      for (int d = tid; d < m; d += kBlock) s_f[d] = A.f[bi + c0 + d];
-      __syncthreads();
-      if (tid == 0)
-        for (int d = 0; d < m; ++d) S = S + s_f[d];
-      __syncthreads();
-    }
-    double a_i = 0.0, F1 = 0.0;
-    if (tid == 0) {
-      const double cs = A.c[ks];
-      a_i = fire_avg(cs, A.v[i], S);
-      F1 = (A.f[ks] + a_i) - cs;
-    }
-    if (kLossy && lost1) {  // the same in every thread of the block
-      if (tid == 0) {
-        A.f[ks] = F1;
-        A.c[ks] = a_i;
-        A.last[i] = a_i;
-        A.fired[i] = 1;
-        n_lost1 += 1;
-      }
-      continue;
-    }
-    S = 0.0;
-    for (int64_t c0 = 0; c0 < dj; c0 += kChunk) {
-      const int m = (int)(dj - c0 < kChunk ? dj - c0 : kChunk);
-      for (int d = tid; d < m; d += kBlock) s_f[d] = A.f[bj + c0 + d];
-      __syncthreads();
-      if (tid == 0) {
-        const int64_t t = kt - bj - c0;  // slot t's place in this chunk, if it is in it
-        for (int d = 0; d < m; ++d) S = S + (d == t ? -F1 : s_f[d]);
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const double a_j = fire_avg(a_i, A.v[j], S);
-      const double F2 = (-F1 + a_j) - a_i;
-      if (kLossy && lost2) {
-        A.f[ks] = F1;
-        A.c[ks] = a_i;
-        n_lost2 += 1;
-      } else {
-        A.f[ks] = -F2;
-        A.c[ks] = a_j;
-      }
-      A.f[kt] = F2;
-      A.c[kt] = a_j;
-      A.last[i] = a_i;
-      A.last[j] = a_j;
-      A.fired[i] = 1;
-      A.fired[j] = 1;
-    }
-  }
-  if constexpr (kLossy) {
-    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
-    if (tid == 0 && n_lost1) atomicAdd(mine, (u64)n_lost1);
-    if (tid == 0 && n_lost2) atomicAdd(mine + 1, (u64)n_lost2);
-  }
+  if constexpr (kLossy) flush_lost_block(A, n_lost1, n_lost2);
 }
 
 // ---- K value columns ------------------------------------------------------------------------
@@ -408,48 +374,27 @@ __device__ inline void row_sums(const double *__restrict__ p, int deg, int K, bo
   }
 }
 
-// kp_exchange for K columns: the same compaction of the block's matched listeners and the same
-// group of 8 lanes per pair. Lane l of a group carries columns l and l + 8 of its pair through
-// both chains. Nothing is staged in LDS: at K columns the two rows of kGroups pairs do not fit
-// it, the loads of a row do not depend on the adds, and across the lanes of a group the loads of
-// f[(b + d) * K + c] are contiguous, as are the writes of f, c and last. So the q0 loop has no
-// barrier, and a lane without a column (l >= K) sits a pair out. Lane 0 writes `fired`, lists a
-// heavy pair and counts the lost messages: once per pair, as in kp_exchange.
+// kp_exchange for K columns: the same compaction and the same group of 8 lanes per pair. Lane l
+// of a group carries columns l and l + 8 of its pair through both chains. Nothing is staged in
+// LDS: at K columns the two rows of kGroups pairs do not fit it, the loads of a row do not
+// depend on the adds, and across the lanes of a group the loads of f[(b + d) * K + c] are
+// contiguous, as are the writes of f, c and last. So the q0 loop has no barrier, and a lane
+// without a column (l >= K) sits a pair out. Lane 0 writes `fired`, lists a heavy pair and
+// counts the lost messages: once per pair, as in kp_exchange.
 template <class Args>
 __global__ __launch_bounds__(kBlock) void kp_exchange_cols(Args A, int K) {
   constexpr bool kLossy = Args::kLossy;
   __shared__ int2 s_pair[kBlock];
-  __shared__ int s_cnt[kBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t node = (int64_t)blockIdx.x * kBlock + tid;
-  u64 word = kNone;
-  if (node < A.n) {
-    word = A.word[node];
-    if (word != kNone) A.word[node] = kNone;
-  }
-  const bool matched = word != kNone;
-  const u64 bal = __ballot(matched);
-  if (lane == 0) s_cnt[w] = __popcll(bal);
-  __syncthreads();
-  int base = 0, np = 0;
-  for (int q = 0; q < kBlock / 64; ++q) {
-    if (q < w) base += s_cnt[q];
-    np += s_cnt[q];
-  }
-  if (matched) s_pair[base + __popcll(bal & ((1ull << lane) - 1))] = make_int2((int)(uint32_t)word, (int)node);
-  __syncthreads();
-  const int g = tid / kGroup, l = tid % kGroup;
+  const int np = compact_matched(A, s_pair);
+  const int tid = threadIdx.x, g = tid / kGroup, l = tid % kGroup;
   const bool two = l + kGroup < K;
-  int n_lost1 = 0, n_lost2 = 0;  // kLossy: this thread's pairs (lane 0 of a group counts)
+  int n_lost1 = 0, n_lost2 = 0;
   for (int q = g; q < np; q += kGroups) {
     const int i = s_pair[q].x, j = s_pair[q].y;
     const int64_t bi = A.rowptr[i], bj = A.rowptr[j];
     const int di = (int)(A.rowptr[i + 1] - bi), dj = (int)(A.rowptr[j + 1] - bj);
     if (di > kLightDeg || dj > kLightDeg) {
-      if (l == 0) {
-        const unsigned slot = atomicAdd(A.n_heavy, 1u);
-        if ((int64_t)slot < A.heavy_cap) A.heavy[slot] = make_int2(i, j);  // always: a heavy row is in one pair
-      }
+      if (l == 0) list_heavy(A, i, j);
       continue;
     }
     const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
@@ -472,38 +417,21 @@ __global__ __launch_bounds__(kBlock) void kp_exchange_cols(Args A, int K) {
         w0 = vj[0];
         w1 = vj[o1];
       }
-      double S0, S1;
+      double S0, S1, ai0, ai1, F10, F11;
       row_sums(A.f + bi * K + l, di, K, two, -1, 0.0, 0.0, S0, S1);
-      const double ai0 = fire_avg(c0, v0, S0), ai1 = fire_avg(c1, v1, S1);
-      const double F10 = (f0 + ai0) - c0, F11 = (f1 + ai1) - c1;
-      if (kLossy && lost1) {  // i fired into a message nobody received
-        fs[0] = F10;
-        cs[0] = ai0;
-        li[0] = ai0;
-        if (two) {
-          fs[kGroup] = F11;
-          cs[kGroup] = ai1;
-          li[kGroup] = ai1;
-        }
+      fire(f0, c0, v0, S0, ai0, F10);
+      fire(f1, c1, v1, S1, ai1, F11);
+      if (kLossy && lost1) {
+        fired_unheard(fs, cs, li, F10, ai0);
+        if (two) fired_unheard(fs + kGroup, cs + kGroup, li + kGroup, F11, ai1);
       } else {
         row_sums(A.f + bj * K + l, dj, K, two, (int)(kt - bj), -F10, -F11, S0, S1);
-        const double aj0 = fire_avg(ai0, w0, S0), aj1 = fire_avg(ai1, w1, S1);
-        const double F20 = (-F10 + aj0) - ai0, F21 = (-F11 + aj1) - ai1;
-        const bool kept = kLossy && lost2;  // j answered, i never heard it: i keeps what it fired
-        fs[0] = kept ? F10 : -F20;
-        cs[0] = kept ? ai0 : aj0;
-        ft[0] = F20;
-        ct[0] = aj0;
-        li[0] = ai0;
-        lj[0] = aj0;
-        if (two) {
-          fs[kGroup] = kept ? F11 : -F21;
-          cs[kGroup] = kept ? ai1 : aj1;
-          ft[kGroup] = F21;
-          ct[kGroup] = aj1;
-          li[kGroup] = ai1;
-          lj[kGroup] = aj1;
-        }
+        double aj0, aj1, F20, F21;
+        fire(-F10, ai0, w0, S0, aj0, F20);
+        fire(-F11, ai1, w1, S1, aj1, F21);
+        const bool kept = kLossy && lost2;
+        settle(fs, cs, ft, ct, li, lj, ai0, aj0, F10, F20, kept);
+        if (two) settle(fs + kGroup, cs + kGroup, ft + kGroup, ct + kGroup, li + kGroup, lj + kGroup, ai1, aj1, F11, F21, kept);
       }
     }
     if (l == 0) {
@@ -517,30 +445,54 @@ __global__ __launch_bounds__(kBlock) void kp_exchange_cols(Args A, int K) {
     }
   }
   if (tid == 0 && np > 0) atomicAdd(A.pairs, (u64)np);
-  if constexpr (kLossy) {
-    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
-    block_count_to<kBlock>(n_lost1, mine);
-    __syncthreads();  // block_count_to's LDS words are read by thread 0 until here
-    block_count_to<kBlock>(n_lost2, mine + 1);
-  }
+  if constexpr (kLossy) flush_lost_block(A, n_lost1, n_lost2);
 }
 
-// kp_heavy for K columns: one block per pair, the rows staged in chunks of kColsChunk doubles,
-// kColsChunk / K slots of K columns each, loaded coalesced as they lie in memory. Threads
-// 0 .. K-1 carry one column's sum each through the chunks in row order (K consecutive LDS words
-// per slot: no bank conflict), first over row i and then, with -F1 in slot t's place, over row j.
-//
-// Args::kLossy: as in kp_heavy, every thread takes the same decision on m1, so the chunk loop of
-// row j, which has barriers, is skipped by all threads or by none.
-template <class Args>
-__global__ __launch_bounds__(kBlock) void kp_heavy_cols(Args A, int K) {
-  constexpr bool kLossy = Args::kLossy;
-  __shared__ double s_f[kColsChunk];
+// ---- heavy pairs ------------------------------------------------------------------------------
+// kp_heavy's sum over one row of K columns (`row` is its first double, `deg` its slots): all
+// threads load a chunk of `chunk` slots coalesced into s_f as they lie in memory, and thread
+// c < K carries column c's sum through the chunk in row order (K consecutive LDS words per slot:
+// no bank conflict), from chunk to chunk. With kSub, slot t of the row counts as r in place of
+// what is stored. Every thread of the block calls it: the barriers are uniform.
+template <bool kSub>
+__device__ inline double heavy_row_sum(const double *row, int64_t deg, int K, int chunk, int64_t t, double r, double *s_f) {
   const int tid = threadIdx.x;
-  const int chunk = kColsChunk / K;  // slots per chunk
+  double S = 0.0;
+  for (int64_t c0 = 0; c0 < deg; c0 += chunk) {
+    const int m = (int)(deg - c0 < chunk ? deg - c0 : chunk);
+    const double *src = row + c0 * K;
+    for (int e = tid; e < m * K; e += kBlock) s_f[e] = src[e];
+    __syncthreads();
+    if (tid < K) {
+      const int64_t tc = t - c0;  // slot t's place in this chunk, if it is in it
+      for (int d = 0; d < m; ++d) S = S + (kSub && d == tc ? r : s_f[d * K + tid]);
+    }
+    __syncthreads();
+  }
+  return S;
+}
+
+// Pairs with a row above kLightDeg: one block per pair, at most kHeavyBlocks blocks sharing the
+// list; first the sum over row i and then, with -F1 in slot t's place, over row j. Two
+// instantiations of one body:
+//   kOne = true, the scalar handle's: K is 1 at compile time, chunks of kChunk slots (8 KB of
+//     LDS), thread 0 carrying; K_ is not read.
+//   kOne = false, a handle of fu_pair_create_k at every K = K_, 1 included: chunks of
+//     kColsChunk / K slots (16 KB), threads 0 .. K-1 carrying a column each.
+//
+// Args::kLossy: every thread holds kt and the loss key, so every thread of the block takes the same
+// decision on m1 and the sum over row j, which has barriers, is skipped by all or by none.
+// Thread 0 writes `fired` and counts the lost messages: once per pair.
+template <class Args, bool kOne>
+__global__ __launch_bounds__(kBlock) void kp_heavy(Args A, int K_) {
+  constexpr bool kLossy = Args::kLossy;
+  __shared__ double s_f[kOne ? kChunk : kColsChunk];
+  const int K = kOne ? 1 : K_;
+  const int chunk = kOne ? kChunk : kColsChunk / K;  // slots per chunk
+  const int tid = threadIdx.x;
   const unsigned listed = *A.n_heavy;
   const unsigned cnt = (int64_t)listed < A.heavy_cap ? listed : (unsigned)A.heavy_cap;
-  unsigned n_lost1 = 0, n_lost2 = 0;  // kLossy: thread 0 counts this block's pairs
+  unsigned n_lost1 = 0, n_lost2 = 0;
   for (unsigned q = blockIdx.x; q < cnt; q += gridDim.x) {
     const int i = A.heavy[q].x, j = A.heavy[q].y;
     const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
@@ -552,68 +504,33 @@ __global__ __launch_bounds__(kBlock) void kp_heavy_cols(Args A, int K) {
       lost1 = message_lost(A, kt);
       lost2 = message_lost(A, ks);
     }
-    double S = 0.0;
-    for (int64_t c0 = 0; c0 < di; c0 += chunk) {
-      const int m = (int)(di - c0 < chunk ? di - c0 : chunk);
-      const double *src = A.f + (bi + c0) * K;
-      for (int e = tid; e < m * K; e += kBlock) s_f[e] = src[e];
-      __syncthreads();
-      if (tid < K)
-        for (int d = 0; d < m; ++d) S = S + s_f[d * K + tid];
-      __syncthreads();
-    }
+    // this thread's column of the pair's cells, if tid < K
+    const int64_t os = ks * K + tid, ot = kt * K + tid, oi = (int64_t)i * K + tid, oj = (int64_t)j * K + tid;
+    double S = heavy_row_sum<false>(A.f + bi * K, di, K, chunk, 0, 0.0, s_f);
     double a_i = 0.0, F1 = 0.0;
-    if (tid < K) {
-      const double cs = A.c[ks * K + tid];
-      a_i = fire_avg(cs, A.v[(int64_t)i * K + tid], S);
-      F1 = (A.f[ks * K + tid] + a_i) - cs;
-    }
+    if (tid < K) fire(A.f[os], A.c[os], A.v[oi], S, a_i, F1);
     if (kLossy && lost1) {  // the same in every thread of the block
-      if (tid < K) {
-        A.f[ks * K + tid] = F1;
-        A.c[ks * K + tid] = a_i;
-        A.last[(int64_t)i * K + tid] = a_i;
-      }
+      if (tid < K) fired_unheard(A.f + os, A.c + os, A.last + oi, F1, a_i);
       if (tid == 0) {
         A.fired[i] = 1;
         n_lost1 += 1;
       }
       continue;
     }
-    S = 0.0;
-    for (int64_t c0 = 0; c0 < dj; c0 += chunk) {
-      const int m = (int)(dj - c0 < chunk ? dj - c0 : chunk);
-      const double *src = A.f + (bj + c0) * K;
-      for (int e = tid; e < m * K; e += kBlock) s_f[e] = src[e];
-      __syncthreads();
-      if (tid < K) {
-        const int64_t t = kt - bj - c0;  // slot t's place in this chunk, if it is in it
-        for (int d = 0; d < m; ++d) S = S + (d == t ? -F1 : s_f[d * K + tid]);
-      }
-      __syncthreads();
-    }
+    S = heavy_row_sum<true>(A.f + bj * K, dj, K, chunk, kt - bj, -F1, s_f);
+    const bool kept = kLossy && lost2;
     if (tid < K) {
-      const double a_j = fire_avg(a_i, A.v[(int64_t)j * K + tid], S);
-      const double F2 = (-F1 + a_j) - a_i;
-      const bool kept = kLossy && lost2;
-      A.f[ks * K + tid] = kept ? F1 : -F2;
-      A.c[ks * K + tid] = kept ? a_i : a_j;
-      A.f[kt * K + tid] = F2;
-      A.c[kt * K + tid] = a_j;
-      A.last[(int64_t)i * K + tid] = a_i;
-      A.last[(int64_t)j * K + tid] = a_j;
+      double a_j, F2;
+      fire(-F1, a_i, A.v[oj], S, a_j, F2);
+      settle(A.f + os, A.c + os, A.f + ot, A.c + ot, A.last + oi, A.last + oj, a_i, a_j, F1, F2, kept);
     }
     if (tid == 0) {
       A.fired[i] = 1;
       A.fired[j] = 1;
-      if (kLossy && lost2) n_lost2 += 1;
+      n_lost2 += kept;
     }
   }
-  if constexpr (kLossy) {
-    u64 *mine = A.lost + (size_t)(blockIdx.x % kLostLines) * kLostStride;
-    if (tid == 0 && n_lost1) atomicAdd(mine, (u64)n_lost1);
-    if (tid == 0 && n_lost2) atomicAdd(mine + 1, (u64)n_lost2);
-  }
+  if constexpr (kLossy) flush_lost_thread0(A, n_lost1, n_lost2);
 }
 
 // How many nodes have never fired: one atomic per block that found some.
@@ -643,7 +560,7 @@ struct fu_pair : handle_base {
   uint64_t loss_seed = 0;
   bool has_mask = false;
   unsigned char *down = nullptr;  // E bytes, allocated when a mask is first set
-  bool cols = false;  // made by fu_pair_create_k: v and last hold n * width doubles, f and c E * width, and the rounds are the *_cols kernels
+  bool cols = false;  // made by fu_pair_create_k: v and last hold n * width doubles, f and c E * width, and the rounds are kp_exchange_cols and kp_heavy<Args, false>
 };
 
 constexpr int kStats = 2 + kLostLines * kLostStride;
@@ -652,15 +569,21 @@ static unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n +
 
 static int launch_err(fu_pair *h, u64 *slot) {
   if (!h->cols) return launch_max_err<kBlock>(h, h->last, slot);
-  static_assert(kBlock == kColsErrBlock, "k_max_err_cols is launched with this file's block");
-  const int K = h->width;
-  const long long total = (long long)h->n * K;
-  const int tb = (kBlock / K) * K;
-  const unsigned grid = (unsigned)std::min<long long>(1024, (total + tb - 1) / tb);
-  hipLaunchKernelGGL(k_max_err_cols, dim3(grid), dim3(kBlock), 0, h->stream, total, K, h->last, h->target,
-                     (const unsigned char *)nullptr, slot);
-  HIP_TRY(hipGetLastError());
-  return FU_OK;
+  return cols_err::launch(h, h->last, /*alive=*/nullptr, slot);
+}
+
+// The exchange of a round in the handle's form, after the matching: K columns (a handle of
+// fu_pair_create_k, at every K) or one, and kp_heavy's instantiation with it.
+template <class Args>
+static void launch_exchange(const fu_pair *h, const Args &X) {
+  const dim3 grid(node_grid(h)), heavy_grid(std::min(h->n_heavy_rows, kHeavyBlocks)), block(kBlock);
+  if (h->cols) {
+    hipLaunchKernelGGL(kp_exchange_cols<Args>, grid, block, 0, h->stream, X, h->width);
+    if (h->n_heavy_rows > 0) hipLaunchKernelGGL((kp_heavy<Args, false>), heavy_grid, block, 0, h->stream, X, h->width);
+  } else {
+    hipLaunchKernelGGL(kp_exchange<Args>, grid, block, 0, h->stream, X);
+    if (h->n_heavy_rows > 0) hipLaunchKernelGGL((kp_heavy<Args, true>), heavy_grid, block, 0, h->stream, X, 1);
+  }
 }
 
 static int launch_round(fu_pair *h) {
@@ -686,31 +609,16 @@ static int launch_round(fu_pair *h) {
       hipLaunchKernelGGL(kp_propose, grid, block, 0, h->stream, A);
     else
       hipLaunchKernelGGL(kp_scan, grid, block, 0, h->stream, A);
-    const dim3 heavy_grid(std::min(h->n_heavy_rows, kHeavyBlocks));
-    const bool lossy = h->p > 0.0 || h->has_mask;
-    LossArgs X;
-    if (lossy) {
+    if (h->p > 0.0 || h->has_mask) {
+      LossArgs X;
       static_cast<RoundArgs &>(X) = A;
       X.down = h->has_mask ? h->down : nullptr;
       X.lost = h->stat + 2;
       X.lkey = loss_key(h->loss_seed, (uint64_t)h->round);
       X.p = h->p;
-    }
-    if (h->cols) {  // a handle of fu_pair_create_k, at every K
-      const int K = h->width;
-      if (lossy) {
-        hipLaunchKernelGGL(kp_exchange_cols<LossArgs>, grid, block, 0, h->stream, X, K);
-        if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy_cols<LossArgs>, heavy_grid, block, 0, h->stream, X, K);
-      } else {
-        hipLaunchKernelGGL(kp_exchange_cols<RoundArgs>, grid, block, 0, h->stream, A, K);
-        if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy_cols<RoundArgs>, heavy_grid, block, 0, h->stream, A, K);
-      }
-    } else if (lossy) {
-      hipLaunchKernelGGL(kp_exchange<LossArgs>, grid, block, 0, h->stream, X);
-      if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy<LossArgs>, heavy_grid, block, 0, h->stream, X);
+      launch_exchange(h, X);
     } else {  // no loss, no mask: the lossless kernels as they always ran
-      hipLaunchKernelGGL(kp_exchange<RoundArgs>, grid, block, 0, h->stream, A);
-      if (h->n_heavy_rows > 0) hipLaunchKernelGGL(kp_heavy<RoundArgs>, heavy_grid, block, 0, h->stream, A);
+      launch_exchange(h, A);
     }
     HIP_TRY(hipGetLastError());
   }

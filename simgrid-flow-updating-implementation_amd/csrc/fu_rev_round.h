@@ -228,7 +228,6 @@ __global__ __launch_bounds__(kBlock) void k_heavy(RoundArgs A, typename R::Args 
 // contiguous read spread over K adjacent lanes. Between the two, a slot's kind sits in s_kind[q]
 // and its two gather indices in the first element of its own LDS rows (s_F[q * K], s_E[q * K],
 // as bit patterns): no LDS beyond the scalar kernels' 34 KB.
-static_assert(kBlock == kColsErrBlock, "k_max_err_cols (fu_handle.h) is launched with this file's block");
 static_assert(kChunk == kTileEdges, "stash_slots and load_elems serve both kernels");
 static_assert(kHeavyDeg * kMaxCols <= kTileEdges, "a light row alone fits a tile at every K");
 
@@ -510,14 +509,7 @@ int launch_rev_round(H *h, const typename R::Args &X) {
 // launch_err of a handle of K > 1 columns: a is the last round's, alive may be null.
 template <typename H>
 int launch_max_err_cols(const H *h, const unsigned char *alive, u64 *slot) {
-  const int K = h->width;
-  const i64 total = (i64)h->n * K;
-  const int tb = (kBlock / K) * K;
-  const unsigned grid = (unsigned)std::min<i64>(1024, (total + tb - 1) / tb);
-  hipLaunchKernelGGL(k_max_err_cols, dim3(grid), dim3(kBlock), 0, h->stream, total, K, h->a[(h->round + 1) & 1], h->target, alive,
-                     slot);
-  HIP_TRY(hipGetLastError());
-  return FU_OK;
+  return cols_err::launch(h, h->a[(h->round + 1) & 1], alive, slot);
 }
 
 // ---- the shared entry points ----------------------------------------------------------------

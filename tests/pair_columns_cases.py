@@ -1,5 +1,5 @@
 """Shared by the tests of the pairwise engine with K value columns (fu.PairwiseSyncBatch;
-csrc/fu_pair.hip kp_exchange_cols and kp_heavy_cols): the widths, the columns, the K-dependent
+csrc/fu_pair.hip kp_exchange_cols and kp_heavy<Args, false>): the widths, the columns, the K-dependent
 chunk of the heavy kernel and a graph whose star centres sit on its edges, and the per-column
 references. The reference of column c is always pair_cases' or pair_loss_cases' restatement run on
 column c alone; nothing here runs the engine.
@@ -17,14 +17,14 @@ from pair_loss_cases import oracle_pair_loss
 # A lane of a pair's group of 8 carries columns l and l + 8: one column, fewer than 8, not a
 # divisor of 8, exactly 8 (no lane has a second), 16 (every lane has two).
 LIGHT_WIDTHS = (1, 2, 3, 5, 8, 16)
-# kp_heavy_cols: threads 0 .. K-1 carry a column each; the chunk shrinks with K.
+# kp_heavy<Args, false>: threads 0 .. K-1 carry a column each; the chunk shrinks with K.
 HEAVY_WIDTHS = (2, 3, 16)
 
 COLS_CHUNK = 2048  # csrc/fu_pair.hip kColsChunk: doubles staged per chunk of a heavy row
 
 
 def chunk_slots(K):
-    """Slots of a heavy row that kp_heavy_cols stages at once at K columns."""
+    """Slots of a heavy row that kp_heavy<Args, false> stages at once at K columns."""
     return COLS_CHUNK // K
 
 
@@ -45,13 +45,14 @@ BOUNDARY_LEAVES = 3000
 
 
 @functools.lru_cache(maxsize=None)
-def boundary_graph(K):
+def boundary_graph(K, n_leaf=BOUNDARY_LEAVES):
     """Star centres of exactly boundary_degrees(K) (node c has degree boundary_degrees(K)[c]),
-    their leaves drawn from a random background graph of 3000 nodes that never touches a
-    centre: pair_cases.class_graph at the K-column kernel's own edges."""
+    their leaves drawn from a random background graph of n_leaf (3000) nodes that never touches
+    a centre: pair_cases.class_graph at the K-column kernel's own edges. A centre's leaves are
+    distinct, so K = 1 (a centre of 4097 slots) needs more leaves than the default."""
     rng = np.random.default_rng(100 + K)
     degs = boundary_degrees(K)
-    k, n_leaf = len(degs), BOUNDARY_LEAVES
+    k = len(degs)
     src, dst = [], []
     for c, d in enumerate(degs):
         src.append(np.full(d, c))

@@ -1,4 +1,4 @@
-"""fu.PairwiseSyncBatch (csrc/fu_pair.hip kp_exchange_cols and kp_heavy_cols, lossless and lossy):
+"""fu.PairwiseSyncBatch (csrc/fu_pair.hip kp_exchange_cols and kp_heavy<Args, false>, lossless and lossy):
 every column of a K-column run holds the bits of that column's own reference, which never runs
 the engine: pair_cases.oracle_pair or pair_loss_cases.oracle_pair_loss (the C oracle's replay),
 pair_loss_python where inputs and seeds change between runs, and the reference's value-domain
