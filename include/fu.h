@@ -450,6 +450,22 @@ int fu_churn_live(int32_t n, const int64_t *rowptr, const int32_t *col, const in
  * message delivered over it, in either direction, restores that (PW:98-99). With p = 0 and no
  * mask the handle launches the lossless kernels; with p = 1 every initiator fires alone.
  * Arguments are checked before any HIP call, also on a host without a GPU.
+ *
+ * Churn (fu_pair_set_topology; after create every slot is live). The topology is fu_churn's:
+ * the pair (alive[n], link_up[e]) given whole at every call, slot k = (i -> j) live iff
+ * link_up[k] && alive[i] && alive[j] (fu_churn_live). A call moves a slot
+ *   live -> not live: f[k] = c[k] = +0.0 in every column, on both ends (both drop the neighbour
+ *                     and its `flows` and `estimates` entries, whatever a lost answer left there);
+ *   not live -> live: nothing: the cells hold +0.0, a neighbour just added (PW:33-34, PW:94-96);
+ *   live -> live:     as it was.
+ * last, the fired flags and the values are untouched. The matching of a round is the rule above
+ * on the live subgraph: with ldeg_i the live slots of row i, a dead node or one with ldeg_i == 0
+ * is idle, a proposer takes its p_i-th live slot in row order, p_i = (h_i >> 1) % ldeg_i, and
+ * validity and priority are unchanged; fu_pair_matching_live restates it on the host. The
+ * exchange is unchanged but for the chosen slot, and a fire's sum S runs over the live slots
+ * only. Loss and mask compose with no further rule: their decisions stay on the caller's slot
+ * index. With everything live this is the engine without a topology, bit for bit. Once a
+ * topology has been set, max_err and the error trace run over the alive nodes only (+0.0 if none).
  * ==================================================================================== */
 typedef struct fu_pair fu_pair;
 
@@ -485,6 +501,16 @@ int fu_pair_set_loss(fu_pair *h, double p, uint64_t seed);
 /* down[e]: a non-zero byte loses every message received on slot k in the rounds run after the
  * call. NULL clears the mask. */
 int fu_pair_set_link_mask(fu_pair *h, const uint8_t *down);
+/* alive[n], link_up[e]: non-zero = on, NULL = all ones; the whole topology of the rounds run
+ * after the call, queued behind the rounds already queued (synchronises). link_up must agree on
+ * a slot and its reverse: FU_ERR_ARG naming the first offending slot, checked on the host before
+ * any HIP call. fu_pair_reset keeps the topology. */
+int fu_pair_set_topology(fu_pair *h, const uint8_t *alive, const uint8_t *link_up);
+/* out[0] = alive nodes, out[1] = live directed slots of the current topology (n and e before
+ * any topology call). */
+int fu_pair_get_topology_stats(fu_pair *h, int64_t out[2]);
+/* out[e]: 1 where the slot is live, else 0. */
+int fu_pair_get_slot_live(fu_pair *h, uint8_t *out /* e */);
 /* "match": how the device finds the matching, 0 = proposers push one 64-bit atomicMin per valid
  * proposal (default), 1 = every listener hashes its own row. Same matching, same bits; the
  * switch exists for the A/B of tools/bench_pair.py. Unknown key or value: FU_ERR_ARG. */
@@ -493,7 +519,7 @@ int fu_pair_set_option(fu_pair *h, const char *key, int64_t value);
  * are kept. */
 int fu_pair_set_values(fu_pair *h, const double *value);
 /* Zero the state, the round counter and the statistics (the loss counters too). The seeds, the
- * loss, the mask and the values are kept. */
+ * loss, the mask, the topology and the values are kept. */
 int fu_pair_reset(fu_pair *h);
 /* Run `rounds` rounds. If err_every > 0 (targets required), err_trace receives, after every
  * err_every-th round, max_i |last_i - target_i| (rounds / err_every entries; the maximum is
@@ -524,6 +550,11 @@ int fu_pair_destroy(fu_pair *h);
  * initiator[i] = 1 for the proposer of a pair, else 0. */
 int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed,
                      int64_t round, int32_t *mate /* n */, uint8_t *initiator /* n */);
+/* The same under a topology (alive[n], link_up[e], NULL = all ones; both NULL is
+ * fu_pair_matching). The graph must be symmetric; link_up as for fu_pair_set_topology. */
+int fu_pair_matching_live(int32_t n, const int64_t *rowptr, const int32_t *col,
+                          const uint8_t *alive, const uint8_t *link_up, uint64_t seed,
+                          int64_t round, int32_t *mate /* n */, uint8_t *initiator /* n */);
 /* Host only, no GPU: out[q] = 1 if the message received on slot first + q in round `round` is
  * lost under (p, seed), no mask. */
 int fu_pair_lost(uint64_t seed, int64_t round, int64_t first, int64_t count, double p,

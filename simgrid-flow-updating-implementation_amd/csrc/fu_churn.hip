@@ -31,9 +31,10 @@
 //
 // This file holds the churn rule (the state byte is the slot's kind: UP gathers, DOWN is
 // skipped, FRESH is kZero and turns UP at write-out; a dead row does not fire), the topology
-// pass and the error check over alive nodes. The round itself (the kernels, the launch plan,
-// the common buffers, the front half of create) is csrc/fu_rev_round.h, shared with the lossy
-// engine; the handle scaffold under it is csrc/fu_handle.h.
+// pass; the error check over alive nodes is the scaffold's k_max_err_alive. The round itself
+// (the kernels, the launch plan, the common buffers, the front half of create) is
+// csrc/fu_rev_round.h, shared with the lossy engine; the handle scaffold under it is
+// csrc/fu_handle.h.
 #include "fu_rev_round.h"
 
 using namespace fu;
@@ -87,32 +88,6 @@ __global__ __launch_bounds__(kBlock) void kc_topology(int n, i64 E, const int *_
   block_count_to<kBlock>(live, count + 1);
 }
 
-// k_max_err of the scaffold over the alive nodes only: a dead node's frozen estimate never
-// enters the maximum, and with no node alive the slot keeps its +0.0.
-__global__ __launch_bounds__(kBlock) void kc_max_err(int n, const double *__restrict__ a, const double *__restrict__ target,
-                                                     const unsigned char *__restrict__ alive, u64 *__restrict__ err) {
-  u64 m = 0;
-  for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < n; i += (i64)gridDim.x * kBlock) {
-    if (!alive[i]) continue;
-    const u64 x = (u64)__double_as_longlong(fabs(a[i] - target[i]));
-    m = x > m ? x : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 y = __shfl_xor(m, off, 64);
-    m = m > y ? m : y;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
-}
-
-// A link is up or down as a whole: FU_ERR_ARG where link_up (may be null: all ones) differs
-// between a slot and its reverse. rev has passed check_rev.
-int check_link_up(const char *who, int64_t e, const int32_t *rev, const uint8_t *link_up) {
-  for (int64_t k = 0; link_up && k < e; ++k)
-    if ((link_up[k] != 0) != (link_up[rev[k]] != 0))
-      return fail(FU_ERR_ARG, std::string(who) + ": link_up differs between slot " + std::to_string(k) + " and its reverse");
-  return FU_OK;
-}
-
 }  // namespace
 
 struct fu_churn : rev_handle {
@@ -125,11 +100,7 @@ struct fu_churn : rev_handle {
 
 static int launch_err(fu_churn *h, u64 *slot) {
   if (h->width > 1) return launch_max_err_cols(h, h->alive, slot);
-  const unsigned grid = (unsigned)std::min<int64_t>(1024, ((int64_t)h->n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(kc_max_err, dim3(grid), dim3(kBlock), 0, h->stream, h->n, h->a[(h->round + 1) & 1], h->target, h->alive,
-                     slot);  // a of the last round run
-  HIP_TRY(hipGetLastError());
-  return FU_OK;
+  return launch_max_err_alive<kBlock>(h, h->a[(h->round + 1) & 1], h->alive, slot);  // a of the last round run
 }
 
 static int launch_round(fu_churn *h) { return launch_rev_round<churn_rule>(h, {h->alive, h->state}); }

@@ -75,6 +75,25 @@ __global__ __launch_bounds__(BLOCK) void k_max_err(int n, const double *__restri
   if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
 }
 
+// k_max_err over the alive nodes only (the churn engine's and the pair engine's under a
+// topology): a dead node's frozen estimate never enters the maximum, and with no node alive the
+// slot keeps its +0.0.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_max_err_alive(int n, const double *__restrict__ a, const double *__restrict__ target,
+                                                         const unsigned char *__restrict__ alive, u64 *__restrict__ err) {
+  u64 m = 0;
+  for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+    if (!alive[i]) continue;
+    const u64 x = (u64)__double_as_longlong(fabs(a[i] - target[i]));
+    m = x > m ? x : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 y = __shfl_xor(m, off, 64);
+    m = m > y ? m : y;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(err, m);
+}
+
 // The block's sum of cnt, added to *dst with one atomic if it is not zero. Every thread of the
 // block calls it; cnt is left holding its wave's sum.
 template <int BLOCK>
@@ -202,6 +221,24 @@ int launch_max_err(const handle_base *h, const double *a, u64 *slot) {
   const unsigned grid = (unsigned)std::min<int64_t>(1024, ((int64_t)h->n + BLOCK - 1) / BLOCK);
   hipLaunchKernelGGL(k_max_err<BLOCK>, dim3(grid), dim3(BLOCK), 0, h->stream, h->n, a, h->target, slot);
   HIP_TRY(hipGetLastError());
+  return FU_OK;
+}
+
+// The same over the alive nodes only.
+template <int BLOCK>
+int launch_max_err_alive(const handle_base *h, const double *a, const unsigned char *alive, u64 *slot) {
+  const unsigned grid = (unsigned)std::min<int64_t>(1024, ((int64_t)h->n + BLOCK - 1) / BLOCK);
+  hipLaunchKernelGGL(k_max_err_alive<BLOCK>, dim3(grid), dim3(BLOCK), 0, h->stream, h->n, a, h->target, alive, slot);
+  HIP_TRY(hipGetLastError());
+  return FU_OK;
+}
+
+// A link is up or down as a whole: FU_ERR_ARG where link_up (may be null: all ones) differs
+// between a slot and its reverse. rev has passed check_rev.
+inline int check_link_up(const char *who, int64_t e, const int32_t *rev, const uint8_t *link_up) {
+  for (int64_t k = 0; link_up && k < e; ++k)
+    if ((link_up[k] != 0) != (link_up[rev[k]] != 0))
+      return fail(FU_ERR_ARG, std::string(who) + ": link_up differs between slot " + std::to_string(k) + " and its reverse");
   return FU_OK;
 }
 

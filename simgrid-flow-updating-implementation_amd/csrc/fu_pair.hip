@@ -57,6 +57,26 @@
 // list_heavy and the two flushes of the lost-message counters. The two exchange kernels differ
 // on purpose; the heavy kernel is one body in two instantiations.
 //
+// Under a topology (fu_pair_set_topology) slot k = (i -> j) is live iff
+// link_up[k] && alive[i] && alive[j], the churn engine's rule, and the handle keeps one live byte
+// per slot and the live degree ldeg_i per node. kp_topology turns the uploaded masks into both; a
+// slot that stops being live loses f and c in every column (+0.0: both ends drop the neighbour),
+// one that becomes live keeps the +0.0 it holds (a neighbour just added, PW:33-34). The matching
+// is the rule above on the live subgraph: a node with ldeg_i == 0 (a dead node has none) is idle,
+// a proposer takes its p_i-th live slot in row order, p_i = (h_i >> 1) % ldeg_i; live_proposal
+// below states it once for the kernels and fu_pair_matching_live. kp_pick writes the chosen slot
+// into pick[i] (and pushes the proposal, form A; form B's kp_scan_live reads pick), and the
+// <Topo<..>> instantiations of the exchange kernels take ks = pick[i] (if constexpr) in place of
+// rowptr[i] + pair_slot(h_i, deg_i); kt = rev[ks] is live too, liveness being symmetric. Nothing
+// else in them changes. The row sums keep running over the whole CSR row:
+//   1. a dropped slot holds +0.0 (kp_topology wrote it, or it was never written);
+//   2. no pair ever writes a dropped slot: only ks and kt are written, and both are live;
+//   3. S starts from +0.0, and x + y is -0.0 only where x and y both are;
+//   4. so S is never -0.0, and S + (+0.0) == S bit for bit, a NaN included;
+//   5. hence the sum equals the reference's sum over the live neighbours only.
+// The light/heavy split stays by CSR degree, and the loss decisions stay on the caller's slot
+// index. A handle that never got a topology call launches the kernels it always launched.
+//
 // The handle scaffold (create and destroy, the run loops, the error slots and k_max_err, the
 // small entry points) is csrc/fu_handle.h, shared with the batched and lossy engines; the
 // per-column error reduction, kernel and launch, is csrc/fu_cols_err.h, shared with the
@@ -120,6 +140,42 @@ struct RoundArgs {
   int32_t heavy_cap;
   uint64_t key;          // round_key(seed, r)
   static constexpr bool kLossy = false;
+  static constexpr bool kTopo = false;
+};
+
+// The rule under a topology: does node i propose in the round keyed `key`? If so ks is the slot
+// it proposes over, the p_i-th live one of its row, and pk its priority at the listener
+// col[ks]; whether that listener listens is the caller's to ask. `live` holds a byte per slot
+// and ldeg the live slots per row (0 for a dead node).
+FU_HD inline bool live_proposal(uint64_t key, int32_t i, const int64_t *rowptr, const unsigned char *live,
+                                const int32_t *ldeg, int64_t &ks, uint64_t &pk) {
+  const uint64_t h = splitmix_at(key, (uint64_t)i);
+  if (!(h & 1)) return false;  // i listens
+  const int32_t d = ldeg[i];
+  if (d == 0) return false;  // idle
+  int64_t p = pair_slot(h, d);
+  for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+    if (live[k] && p-- == 0) {
+      ks = k;
+      pk = ((h >> 32) << 32) | (uint64_t)(uint32_t)i;
+      return true;
+    }
+  return false;  // never: the row has ldeg[i] live bytes
+}
+
+// What the topology forms of the matching kernels read and write beside RoundArgs.
+struct TopoArgs {
+  const unsigned char *live;  // per slot
+  const int32_t *ldeg;        // per node: live slots of its row
+  int32_t *pick;              // per node: the slot a proposer chose this round, or -1
+};
+
+// The arguments of the topology instantiations of kp_exchange, kp_exchange_cols and kp_heavy,
+// over RoundArgs or LossArgs: ks comes from pick.
+template <class Base>
+struct Topo : Base {
+  const int32_t *pick;
+  static constexpr bool kTopo = true;
 };
 
 // The arguments of the lossy instantiations of kp_exchange, kp_exchange_cols and kp_heavy; a
@@ -217,6 +273,76 @@ __global__ __launch_bounds__(kBlock) void kp_scan(RoundArgs A) {
   if (best != kNone) A.word[j] = best;
 }
 
+// ---- the matching under a topology ---------------------------------------------------------
+// Launched only once a topology has been set. Every proposer finds its chosen live slot from the
+// live bytes of its row (contiguous; one thread a row, a long row included) and records it in
+// pick[i] for the exchange. kPush (form A): a valid proposal goes into the listener's word as in
+// kp_propose, and only proposers write pick. Without kPush (form B) every node writes pick, -1
+// if it does not propose, and kp_scan_live reads it.
+template <bool kPush>
+__global__ __launch_bounds__(kBlock) void kp_pick(RoundArgs A, TopoArgs T) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *A.n_heavy = 0;  // the list of the round before has been consumed
+  if (i >= A.n) return;
+  int64_t ks;
+  uint64_t pk;
+  const bool proposes = live_proposal(A.key, (int32_t)i, A.rowptr, T.live, T.ldeg, ks, pk);
+  if (!kPush || proposes) T.pick[i] = proposes ? (int32_t)ks : -1;
+  if (kPush && proposes) {
+    const int32_t j = A.col[ks];
+    if (!(splitmix_at(A.key, (uint64_t)j) & 1)) atomicMin(&A.word[j], (u64)pk);
+  }
+}
+
+// Form B: listener j takes the smallest key among the neighbours whose pick is the reverse of
+// one of its live slots. No atomics; kp_pick<false> of the same round has run.
+__global__ __launch_bounds__(kBlock) void kp_scan_live(RoundArgs A, TopoArgs T) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= A.n) return;
+  if (splitmix_at(A.key, (uint64_t)j) & 1) return;
+  if (T.ldeg[j] == 0) return;
+  u64 best = kNone;
+  for (int64_t k = A.rowptr[j]; k < A.rowptr[j + 1]; ++k) {
+    if (!T.live[k]) continue;
+    const int32_t i = A.col[k];
+    if (T.pick[i] != A.rev[k]) continue;
+    const u64 pk = ((splitmix_at(A.key, (uint64_t)i) >> 32) << 32) | (u64)(uint32_t)i;
+    best = pk < best ? pk : best;
+  }
+  if (best != kNone) A.word[j] = best;
+}
+
+// fu_pair_set_topology: one pass over the slots, from the uploaded alive and link_up and the
+// old live byte to the new one. Slot k's row is col[rev k]. A slot that stops being live loses
+// its K doubles of f and of c; a live slot adds one to its row's ldeg, zeroed before the launch.
+// count[0] += alive nodes, count[1] += live slots, one atomic per block and counter; the grid
+// covers max(E, n) threads, so every node is counted where E is small.
+__global__ __launch_bounds__(kBlock) void kp_topology(int n, int64_t E, const int32_t *__restrict__ col,
+                                                      const int32_t *__restrict__ rev, const unsigned char *__restrict__ alive,
+                                                      const unsigned char *__restrict__ link_up, unsigned char *__restrict__ live,
+                                                      int32_t *__restrict__ ldeg, double *__restrict__ f, double *__restrict__ c,
+                                                      int K, u64 *__restrict__ count) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int now = 0;
+  if (k < E) {
+    const int32_t row = col[rev[k]];
+    now = link_up[k] != 0 && alive[row] != 0 && alive[col[k]] != 0;
+    if (now) {
+      atomicAdd(&ldeg[row], 1);
+    } else if (live[k]) {
+      for (int q = 0; q < K; ++q) {
+        f[k * K + q] = 0.0;
+        c[k * K + q] = 0.0;
+      }
+    }
+    live[k] = (unsigned char)now;
+  }
+  int up = k < n && alive[k] != 0;
+  block_count_to<kBlock>(up, count);
+  __syncthreads();  // block_count_to's wave sums are one LDS array: the first call has read it
+  block_count_to<kBlock>(now, count + 1);
+}
+
 // ---- the exchange ------------------------------------------------------------------------
 // Thread t of block b looks at node b * kBlock + t: a listener whose word holds a key is
 // matched with the key's low half, and writes the word back to kNone. The block compacts its
@@ -279,7 +405,10 @@ __global__ __launch_bounds__(kBlock) void kp_exchange(Args A) {
         if (l == 0) list_heavy(A, i, j);
       } else {
         light = true;
-        ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+        if constexpr (Args::kTopo)
+          ks = A.pick[i];  // the proposer's chosen live slot (kp_pick)
+        else
+          ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
         for (int d = l; d < di; d += kGroup) s_f[g][d] = A.f[bi + d];
         if constexpr (kLossy) {
           const int64_t kt = A.rev[ks];  // in row j: fu_pair_create checked rev as a pairing
@@ -397,7 +526,11 @@ __global__ __launch_bounds__(kBlock) void kp_exchange_cols(Args A, int K) {
       if (l == 0) list_heavy(A, i, j);
       continue;
     }
-    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+    int64_t ks;
+    if constexpr (Args::kTopo)
+      ks = A.pick[i];  // the proposer's chosen live slot (kp_pick)
+    else
+      ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
     const int64_t kt = A.rev[ks];  // in row j: fu_pair_create_k checked rev as a pairing
     bool lost1 = false, lost2 = false;
     if constexpr (kLossy) {
@@ -497,7 +630,11 @@ __global__ __launch_bounds__(kBlock) void kp_heavy(Args A, int K_) {
     const int i = A.heavy[q].x, j = A.heavy[q].y;
     const int64_t bi = A.rowptr[i], di = A.rowptr[i + 1] - bi;
     const int64_t bj = A.rowptr[j], dj = A.rowptr[j + 1] - bj;
-    const int64_t ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
+    int64_t ks;
+    if constexpr (Args::kTopo)
+      ks = A.pick[i];  // the proposer's chosen live slot (kp_pick)
+    else
+      ks = bi + pair_slot(splitmix_at(A.key, (uint64_t)i), di);
     const int64_t kt = A.rev[ks];
     bool lost1 = false, lost2 = false;
     if constexpr (kLossy) {
@@ -560,6 +697,14 @@ struct fu_pair : handle_base {
   uint64_t loss_seed = 0;
   bool has_mask = false;
   unsigned char *down = nullptr;  // E bytes, allocated when a mask is first set
+  // The topology (fu_pair_set_topology). Until the first call every slot is live, none of the
+  // buffers exists and the rounds are the ones without a topology.
+  bool has_topo = false;
+  unsigned char *alive = nullptr, *link_up = nullptr, *live = nullptr;  // n, E, E bytes
+  int32_t *ldeg = nullptr, *pick = nullptr;                             // n each
+  u64 *count = nullptr;                                                 // kp_topology's two counters
+  std::vector<int32_t> h_rev;  // host copy: the symmetry check of link_up
+  int64_t topo_stats[2] = {0, 0};  // alive nodes, live slots of the current topology
   bool cols = false;  // made by fu_pair_create_k: v and last hold n * width doubles, f and c E * width, and the rounds are kp_exchange_cols and kp_heavy<Args, false>
 };
 
@@ -568,8 +713,10 @@ constexpr int kStats = 2 + kLostLines * kLostStride;
 static unsigned node_grid(const fu_pair *h) { return (unsigned)(((int64_t)h->n + kBlock - 1) / kBlock); }
 
 static int launch_err(fu_pair *h, u64 *slot) {
-  if (!h->cols) return launch_max_err<kBlock>(h, h->last, slot);
-  return cols_err::launch(h, h->last, /*alive=*/nullptr, slot);
+  const unsigned char *alive = h->has_topo ? h->alive : nullptr;  // once a topology is set: over the alive nodes
+  if (h->cols) return cols_err::launch(h, h->last, alive, slot);
+  if (alive) return launch_max_err_alive<kBlock>(h, h->last, alive, slot);
+  return launch_max_err<kBlock>(h, h->last, slot);
 }
 
 // The exchange of a round in the handle's form, after the matching: K columns (a handle of
@@ -584,6 +731,16 @@ static void launch_exchange(const fu_pair *h, const Args &X) {
     hipLaunchKernelGGL(kp_exchange<Args>, grid, block, 0, h->stream, X);
     if (h->n_heavy_rows > 0) hipLaunchKernelGGL((kp_heavy<Args, true>), heavy_grid, block, 0, h->stream, X, 1);
   }
+}
+
+// launch_exchange with the handle's topology, if it has one: the <Topo<Args>> instantiations.
+template <class Args>
+static void launch_in_topology(const fu_pair *h, const Args &X) {
+  if (!h->has_topo) return launch_exchange(h, X);
+  Topo<Args> Y;
+  static_cast<Args &>(Y) = X;
+  Y.pick = h->pick;
+  launch_exchange(h, Y);
 }
 
 static int launch_round(fu_pair *h) {
@@ -605,10 +762,19 @@ static int launch_round(fu_pair *h) {
   A.key = round_key(h->seed, (uint64_t)h->round);
   if (h->E > 0) {  // without edges every node is idle
     const dim3 grid(node_grid(h)), block(kBlock);
-    if (h->match == 0)
+    if (h->has_topo) {
+      const TopoArgs T{h->live, h->ldeg, h->pick};
+      if (h->match == 0) {
+        hipLaunchKernelGGL(kp_pick<true>, grid, block, 0, h->stream, A, T);
+      } else {
+        hipLaunchKernelGGL(kp_pick<false>, grid, block, 0, h->stream, A, T);
+        hipLaunchKernelGGL(kp_scan_live, grid, block, 0, h->stream, A, T);
+      }
+    } else if (h->match == 0) {
       hipLaunchKernelGGL(kp_propose, grid, block, 0, h->stream, A);
-    else
+    } else {
       hipLaunchKernelGGL(kp_scan, grid, block, 0, h->stream, A);
+    }
     if (h->p > 0.0 || h->has_mask) {
       LossArgs X;
       static_cast<RoundArgs &>(X) = A;
@@ -616,9 +782,9 @@ static int launch_round(fu_pair *h) {
       X.lost = h->stat + 2;
       X.lkey = loss_key(h->loss_seed, (uint64_t)h->round);
       X.p = h->p;
-      launch_exchange(h, X);
+      launch_in_topology(h, X);
     } else {  // no loss, no mask: the lossless kernels as they always ran
-      launch_exchange(h, A);
+      launch_in_topology(h, A);
     }
     HIP_TRY(hipGetLastError());
   }
@@ -645,7 +811,8 @@ extern "C" {
 
 int fu_pair_destroy(fu_pair *h) {
   if (!h) return bad_arguments<fu_pair>("destroy");
-  handle_close(h, {h->rowptr, h->col, h->rev, h->v, h->f, h->c, h->last, h->word, h->fired, h->heavy, h->n_heavy, h->stat, h->down});
+  handle_close(h, {h->rowptr, h->col, h->rev, h->v, h->f, h->c, h->last, h->word, h->fired, h->heavy, h->n_heavy, h->stat, h->down,
+                   h->alive, h->link_up, h->live, h->ldeg, h->pick, h->count});
   delete h;
   return FU_OK;
 }
@@ -668,6 +835,9 @@ static int pair_create(const char *entry, int32_t n, int64_t e, const int64_t *r
   auto *h = new fu_pair();
   h->n_heavy_rows = heavy_rows;
   h->cols = cols;
+  if (e > 0) h->h_rev.assign(rev, rev + e);
+  h->topo_stats[0] = n;
+  h->topo_stats[1] = e;
   auto cleanup = [&](int code) { fu_pair_destroy(h); return code; };
   int rc = FU_OK;
   if ((rc = handle_open(h, device, n, e, k))) return cleanup(rc);
@@ -744,6 +914,78 @@ int fu_pair_set_link_mask(fu_pair *h, const uint8_t *down) {
   h->has_mask = true;
   return FU_OK;
   FU_TRY_END
+}
+
+// The first call allocates the topology's buffers, every slot live as it has been since create.
+// Each buffer is guarded by its own pointer: a call after a failed one allocates only what is missing.
+static int topology_buffers(fu_pair *h) {
+  if (h->live) return FU_OK;
+  int rc = FU_OK;
+  if ((!h->alive && (rc = dmalloc(h, &h->alive, h->n))) || (!h->link_up && (rc = dmalloc(h, &h->link_up, h->E))) ||
+      (!h->ldeg && (rc = dmalloc(h, &h->ldeg, h->n))) || (!h->pick && (rc = dmalloc(h, &h->pick, h->n))) ||
+      (!h->count && (rc = dmalloc(h, &h->count, 2))))
+    return rc;
+  unsigned char *live = nullptr;
+  if ((rc = dmalloc(h, &live, h->E))) return rc;
+  if (hipMemsetAsync(live, 1, (size_t)std::max<int64_t>(h->E, 1), h->stream) != hipSuccess) {
+    (void)hipFree(live);
+    return fail(FU_ERR_HIP, "fu_pair_set_topology: memset failed");
+  }
+  h->live = live;
+  return FU_OK;
+}
+
+int fu_pair_set_topology(fu_pair *h, const uint8_t *alive, const uint8_t *link_up) {
+  FU_TRY_BEGIN
+  if (!h) return bad_arguments<fu_pair>("set_topology");
+  if (int rc = check_link_up("fu_pair_set_topology", h->E, h->h_rev.data(), link_up)) return rc;
+  if (int rc = set_device(h)) return rc;
+  if (int rc = topology_buffers(h)) return rc;
+  // over the handle's stream: the rounds queued before the call run under the old topology
+  if (alive)
+    HIP_TRY(hipMemcpyAsync(h->alive, alive, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+  else
+    HIP_TRY(hipMemsetAsync(h->alive, 1, (size_t)h->n, h->stream));
+  if (h->E > 0) {
+    if (link_up)
+      HIP_TRY(hipMemcpyAsync(h->link_up, link_up, (size_t)h->E, hipMemcpyHostToDevice, h->stream));
+    else
+      HIP_TRY(hipMemsetAsync(h->link_up, 1, (size_t)h->E, h->stream));
+  }
+  HIP_TRY(hipMemsetAsync(h->ldeg, 0, sizeof(int32_t) * (size_t)h->n, h->stream));
+  HIP_TRY(hipMemsetAsync(h->count, 0, 2 * sizeof(u64), h->stream));
+  const int64_t work = std::max<int64_t>(h->E, h->n);
+  hipLaunchKernelGGL(kp_topology, dim3((unsigned)((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->n, h->E, h->col,
+                     h->rev, h->alive, h->link_up, h->live, h->ldeg, h->f, h->c, h->width, h->count);
+  HIP_TRY(hipGetLastError());
+  // The pass is queued: the live bytes and the cells are the new topology's whatever follows, so
+  // the rounds launched from now on take the topology kernels even if the counts cannot be read
+  // (FU_ERR_HIP then, with the statistics of the call before).
+  h->has_topo = true;
+  u64 c[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(c, h->count, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->topo_stats[0] = (int64_t)c[0];
+  h->topo_stats[1] = (int64_t)c[1];
+  return FU_OK;
+  FU_TRY_END
+}
+
+int fu_pair_get_topology_stats(fu_pair *h, int64_t out[2]) {
+  if (!h || !out) return bad_arguments<fu_pair>("get_topology_stats");
+  out[0] = h->topo_stats[0];
+  out[1] = h->topo_stats[1];
+  return FU_OK;
+}
+
+// Before the first topology call every slot is live and no buffer holds that.
+int fu_pair_get_slot_live(fu_pair *h, uint8_t *live_out) {
+  if (!h || (!live_out && h->E)) return bad_arguments<fu_pair>("get_slot_live");
+  if (!h->live) {
+    std::fill(live_out, live_out + h->E, (uint8_t)1);
+    return FU_OK;
+  }
+  return download(h, live_out, h->live, (size_t)h->E);
 }
 
 int fu_pair_set_option(fu_pair *h, const char *key, int64_t value) {
@@ -834,18 +1076,32 @@ int fu_pair_lost(uint64_t seed, int64_t round, int64_t first, int64_t count, dou
   return FU_OK;
 }
 
-int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed, int64_t round, int32_t *mate,
-                     uint8_t *initiator) {
-  FU_TRY_BEGIN
-  if (n <= 0 || !rowptr || round < 0 || !mate || !initiator || rowptr[0] != 0 || (rowptr[n] > 0 && !col))
-    return fail(FU_ERR_ARG, "fu_pair_matching: bad arguments");
-  if (int rc = check_csr("fu_pair_matching", n, rowptr[n], rowptr, col)) return rc;
+}  // extern "C"
+
+// fu_pair_matching (live == nullptr) and fu_pair_matching_live (a byte per slot): the proposals
+// of the round into the listeners' words, then the pairs out of them.
+static int host_matching(int32_t n, const int64_t *rowptr, const int32_t *col, const unsigned char *live,
+                         uint64_t seed, int64_t round, int32_t *mate, uint8_t *initiator) {
   const uint64_t key = round_key(seed, (uint64_t)round);
   std::vector<uint64_t> word((size_t)n, (uint64_t)kNone);
+  std::vector<int32_t> ldeg;
+  if (live) {
+    ldeg.assign((size_t)n, 0);
+    for (int32_t i = 0; i < n; ++i)
+      for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k) ldeg[i] += live[k] != 0;
+  }
   for (int32_t i = 0; i < n; ++i) {
     int32_t j;
     uint64_t pk;
-    if (pair_proposal(key, i, rowptr, col, j, pk)) word[j] = std::min(word[j], pk);
+    if (live) {
+      int64_t ks;
+      if (!live_proposal(key, i, rowptr, live, ldeg.data(), ks, pk)) continue;
+      j = col[ks];
+      if (splitmix_at(key, (uint64_t)j) & 1) continue;  // j proposes too
+      word[j] = std::min(word[j], pk);
+    } else if (pair_proposal(key, i, rowptr, col, j, pk)) {
+      word[j] = std::min(word[j], pk);
+    }
   }
   std::fill(mate, mate + n, -1);
   std::fill(initiator, initiator + n, (uint8_t)0);
@@ -857,6 +1113,36 @@ int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint6
       initiator[i] = 1;
     }
   return FU_OK;
+}
+
+extern "C" {
+
+int fu_pair_matching(int32_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed, int64_t round, int32_t *mate,
+                     uint8_t *initiator) {
+  FU_TRY_BEGIN
+  if (n <= 0 || !rowptr || round < 0 || !mate || !initiator || rowptr[0] != 0 || (rowptr[n] > 0 && !col))
+    return fail(FU_ERR_ARG, "fu_pair_matching: bad arguments");
+  if (int rc = check_csr("fu_pair_matching", n, rowptr[n], rowptr, col)) return rc;
+  return host_matching(n, rowptr, col, nullptr, seed, round, mate, initiator);
+  FU_TRY_END
+}
+
+int fu_pair_matching_live(int32_t n, const int64_t *rowptr, const int32_t *col, const uint8_t *alive, const uint8_t *link_up,
+                          uint64_t seed, int64_t round, int32_t *mate, uint8_t *initiator) {
+  FU_TRY_BEGIN
+  if (n <= 0 || !rowptr || round < 0 || !mate || !initiator || rowptr[0] != 0 || (rowptr[n] > 0 && !col))
+    return fail(FU_ERR_ARG, "fu_pair_matching_live: bad arguments");
+  if (!alive && !link_up) return fu_pair_matching(n, rowptr, col, seed, round, mate, initiator);
+  const int64_t e = rowptr[n];
+  const int32_t *rev = nullptr;
+  std::vector<int32_t> built;
+  if (int rc = pairing_rev("fu_pair_matching_live", n, e, rowptr, col, &rev, &built)) return rc;
+  if (int rc = check_link_up("fu_pair_matching_live", e, rev, link_up)) return rc;
+  std::vector<unsigned char> live((size_t)std::max<int64_t>(e, 1));
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+      live[k] = (!link_up || link_up[k] != 0) && (!alive || (alive[i] != 0 && alive[col[k]] != 0));
+  return host_matching(n, rowptr, col, live.data(), seed, round, mate, initiator);
   FU_TRY_END
 }
 

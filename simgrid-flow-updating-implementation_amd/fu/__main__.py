@@ -8,6 +8,7 @@
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs [--pair-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --loss 0.1 [--loss-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --pair-columns 4 [--loss 0.1]
+    python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --pairs --pair-churn 0.1 [--churn-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 [--churn-seed 7]
     python -m fu bench-graph er:n=1000000,m=4000000 --rounds 1000 --churn 0.1 --columns 4   # or --loss
 
@@ -69,7 +70,14 @@ def main(argv=None):
                     help="bench-graph with --loss or --churn: K value columns in one handle (1..16)")
     ap.add_argument("--pair-columns", type=int, default=None,
                     help="bench-graph with --pairs: K value columns over one matching (1..16)")
+    ap.add_argument("--pair-churn", type=float, default=None,
+                    help="bench-graph with --pairs: fraction of the nodes that dies after half of the rounds (pair engine)")
     a = ap.parse_args(argv)
+    if a.pair_churn is not None:
+        if a.mode != "bench-graph" or not a.pairs:
+            ap.error("--pair-churn needs bench-graph with --pairs")
+        if not 0.0 <= a.pair_churn < 1.0:
+            ap.error("--pair-churn must be in [0, 1)")
     if a.pair_columns is not None:
         if a.mode != "bench-graph" or not a.pairs:
             ap.error("--pair-columns needs bench-graph with --pairs")
@@ -115,9 +123,18 @@ def main(argv=None):
         if a.loss is not None:
             eng.set_loss(a.loss, a.loss_seed)
         t0 = time.perf_counter()
-        ms = eng.run_timed(a.rounds)
+        if a.pair_churn is None:
+            ms = eng.run_timed(a.rounds)
+        else:
+            # node i dies iff U_i < FRACTION, U the fu_values_uniform stream at the churn seed
+            alive = ~(uniform_values(g.n, seed=a.churn_seed, lo=0.0, hi=1.0) < a.pair_churn)
+            ms = eng.run_timed(a.rounds // 2)
+            eng.set_topology(alive=alive)
+            ms += eng.run_timed(a.rounds - a.rounds // 2)
         wall = time.perf_counter() - t0
-        if a.pair_columns is None:
+        if a.pair_churn is not None:
+            tgt = churn_targets(g, v, alive)
+        elif a.pair_columns is None:
             tgt, _ = component_means(g.rowptr, g.col, v)
         else:
             tgt = churn_targets(g, v)  # everything alive: component_means per column
@@ -125,6 +142,7 @@ def main(argv=None):
         print(f"graph n={g.n} E={g.E} max_deg={g.max_deg} rounds={a.rounds} "
               f"device_ms={ms:.3f} wall_s={wall:.3f} edge_updates/s={g.E * a.rounds / (ms / 1e3):.4e} "
               f"max_err={np.max(eng.max_err()):.3e} pairs={eng.stats[0]}"
+              + ("" if a.pair_churn is None else f" alive={eng.topology_stats[0]}")
               + ("" if a.loss is None else f" lost={sum(eng.loss_stats[:2])}")
               + ("" if a.pair_columns is None else f" columns={a.pair_columns}"))
         return 0

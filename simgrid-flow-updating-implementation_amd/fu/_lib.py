@@ -155,6 +155,10 @@ _SIGS = {
     "fu_pair_set_link_mask": ([vp, vp], ctypes.c_int),
     "fu_pair_get_loss_stats": ([vp, vp], ctypes.c_int),
     "fu_pair_lost": ([u64, i64, i64, i64, f64, vp], ctypes.c_int),
+    "fu_pair_set_topology": ([vp, vp, vp], ctypes.c_int),
+    "fu_pair_get_topology_stats": ([vp, vp], ctypes.c_int),
+    "fu_pair_get_slot_live": ([vp, vp], ctypes.c_int),
+    "fu_pair_matching_live": ([i32, vp, vp, vp, vp, u64, i64, vp, vp], ctypes.c_int),
     "fu_trace_build": ([i32, vp, vp, i32, i32, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_ex": ([i32, vp, vp, i32, i32, cp, cp, P(vp)], ctypes.c_int),
     "fu_trace_build_routes": ([i32, vp, vp, i32, i32, cp, cp, vp, P(vp)], ctypes.c_int),

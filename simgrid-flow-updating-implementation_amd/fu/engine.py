@@ -498,17 +498,25 @@ class CollectAllChurnBatch(CollectAllChurn):
         self.K = self._cols = int(self.values.shape[1])
 
 
-def pair_matching(g, seed: int, r: int):
+def pair_matching(g, seed: int, r: int, alive=None, link_up=None):
     """(mate, initiator) of round r under `seed` on graph g (a Graph, or a (rowptr, col) pair):
     mate[i] is i's partner or -1, initiator[i] is 1 for the proposer of a pair. The matching of
-    `PairwiseSync` restated on the host (fu_pair_matching; no GPU)."""
+    `PairwiseSync` restated on the host (fu_pair_matching; no GPU). With `alive` (n entries) or
+    `link_up` (E entries) it is the matching under that topology, the rule on the live subgraph
+    (fu_pair_matching_live); both None is the matching without a topology."""
     rowptr, col = (g.rowptr, g.col) if isinstance(g, Graph) else g
     rp = np.ascontiguousarray(rowptr, dtype=np.int64)
     c = np.ascontiguousarray(col, dtype=np.int32)
     n = len(rp) - 1
+    a, u = _mask(alive, n, "alive"), _mask(link_up, len(c), "link_up")
     mate = np.empty(max(n, 1), dtype=np.int32)
     init = np.empty(max(n, 1), dtype=np.uint8)
-    L.call("fu_pair_matching", n, L.ptr(rp), L.ptr(c) if len(c) else None, int(seed), int(r), L.ptr(mate), L.ptr(init))
+    cp = L.ptr(c) if len(c) else None
+    if a is None and u is None:
+        L.call("fu_pair_matching", n, L.ptr(rp), cp, int(seed), int(r), L.ptr(mate), L.ptr(init))
+    else:
+        L.call("fu_pair_matching_live", n, L.ptr(rp), cp, L.ptr(a), L.ptr(u) if len(c) else None, int(seed), int(r),
+               L.ptr(mate), L.ptr(init))
     return mate[:n], init[:n]
 
 
@@ -538,6 +546,12 @@ class PairwiseSync(_Handle):
 
     >>> eng = PairwiseSync(g, uniform_values(g.n, seed=0), seed=7, loss=0.1, loss_seed=3)
     >>> eng.run(2000); first_lost, answers_lost, complete = eng.loss_stats
+
+    `set_topology` switches nodes and links off and on between runs, as `CollectAllChurn` does:
+    the alive nodes converge to `churn_targets`, and the error runs over the alive nodes.
+
+    >>> eng.run(500); alive = np.ones(g.n, np.uint8); alive[:1000] = 0
+    >>> eng.set_topology(alive=alive); eng.set_targets(churn_targets(g, v, alive)); eng.run(2000)
     """
 
     _C = _c_names("fu_pair_")
@@ -572,6 +586,27 @@ class PairwiseSync(_Handle):
         run from now on; None clears the mask."""
         d = _mask(down, self.E, "link_mask")
         L.call("fu_pair_set_link_mask", self._h, L.ptr(d) if d is not None and self.E else None)
+
+    def set_topology(self, alive=None, link_up=None):
+        """alive: n entries, link_up: E entries (the same on a slot and its reverse), non-zero =
+        on, None = all on: the whole topology of the rounds run from now on, `CollectAllChurn`'s.
+        A slot that stops being live loses its flow and cache on both ends; one that becomes live
+        starts from the zeros it holds; the matching runs on the live subgraph."""
+        a, u = _mask(alive, self.n, "alive"), _mask(link_up, self.E, "link_up")
+        L.call("fu_pair_set_topology", self._h, L.ptr(a), L.ptr(u) if self.E else None)
+
+    @property
+    def topology_stats(self) -> tuple:
+        """(alive nodes, live directed slots) of the current topology; (n, E) before any."""
+        s = np.zeros(2, dtype=np.int64)
+        L.call("fu_pair_get_topology_stats", self._h, L.ptr(s))
+        return int(s[0]), int(s[1])
+
+    def slot_live(self) -> np.ndarray:
+        """uint8[E]: 1 where the slot is live."""
+        s = np.empty(max(self.E, 1), dtype=np.uint8)
+        L.call("fu_pair_get_slot_live", self._h, L.ptr(s))
+        return s[:self.E]
 
     def set_option(self, key: str, value: int):
         """"match": 0 = proposers push (atomicMin, default), 1 = listeners scan their rows."""

@@ -35,8 +35,18 @@
    (per column both flow rows, c[s], c[t], v_i, v_j and the six stores; per pair four row
    pointers and one rev).
 
+5. With --churn F: in place of 2, the same two graphs and windows for three scalar handles on the
+   "atomic_min" matching without loss: one that never gets a topology call (the kernels without
+   a topology), one with set_topology() and everything alive (the topology kernels, the same
+   pairs and the same bits: compared before any number is printed), and one with node i dead iff
+   U_i < F (the stream of `python -m fu bench-graph --churn`, at seed 5: independent of the
+   values). reset keeps the topology; the three alternate within each repetition. One JSON line per
+   graph and handle with us_per_round (median, min, max), pairs_per_round, alive, live_slots and
+   ratio_over_no_topology.
+
     python tools/bench_pair.py [--rounds 200] [--n 1000000] [--reps 7] [--skip-replay] [--loss 0.1 0.3]
     python tools/bench_pair.py --skip-replay --columns 1 2 4 8 16
+    python tools/bench_pair.py --skip-replay --churn 0.1
 """
 import argparse
 import ctypes
@@ -56,6 +66,7 @@ from fu import _lib as L  # noqa: E402
 
 PEAK = 8.0e12  # bytes / s
 SEED = 7
+CHURN_SEED = 5  # --churn: which nodes die
 
 
 def round_pairs(g, src, seed, r):
@@ -308,6 +319,45 @@ def big_columns(name, g, rounds, reps, copy_gbs, widths):
             eng.close()
 
 
+def big_churn(name, g, rounds, reps, copy_gbs, frac):
+    """us per round of a handle without a topology, one with everything alive and one with a
+    fraction `frac` of the nodes dead, alternating within each repetition."""
+    v = fu.uniform_values(g.n, seed=0)
+    alive = ~(fu.uniform_values(g.n, seed=CHURN_SEED, lo=0.0, hi=1.0) < frac)  # not the values' stream (seed 0)
+    kinds = ["no_topology", "all_alive", "dead"]
+    engs = [fu.PairwiseSync(g, v, seed=SEED) for _ in kinds]
+    try:
+        engs[1].set_topology()
+        engs[2].set_topology(alive=alive)
+        for eng in engs:
+            eng.run(rounds)  # warm
+        t = [[] for _ in engs]
+        pairs = [0] * len(engs)
+        for _ in range(reps):
+            for q, eng in enumerate(engs):
+                eng.reset()
+                eng.run(1)
+                eng.synchronize()
+                first = eng.stats[0]
+                t[q].append(eng.run_timed(rounds - 1) * 1e3 / (rounds - 1))
+                pairs[q] = eng.stats[0] - first
+        ref = (engs[0].estimates(), engs[0].flows(), engs[0].cache())
+        if not all(same_bits(a, b) for a, b in zip((engs[1].estimates(), engs[1].flows(), engs[1].cache()), ref)):
+            raise SystemExit("bench_pair: the all-alive topology handle differs from the handle without a topology")
+        base = statistics.median(t[0])
+        for q, (eng, kind) in enumerate(zip(engs, kinds)):
+            us = statistics.median(t[q])
+            n_alive, n_live = eng.topology_stats
+            print(json.dumps({"graph": name, "n": g.n, "E": g.E, "handle": kind, "churn": frac if kind == "dead" else 0.0,
+                              "alive": n_alive, "live_slots": n_live, "rounds_timed": [1, rounds - 1], "reps": reps,
+                              "us_per_round": round(us, 2), "us_per_round_min": round(min(t[q]), 2),
+                              "us_per_round_max": round(max(t[q]), 2), "pairs_per_round": round(pairs[q] / (rounds - 1), 1),
+                              "ratio_over_no_topology": round(us / base, 4), "copy_GBs": copy_gbs}), flush=True)
+    finally:
+        for eng in engs:
+            eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
@@ -318,7 +368,11 @@ def main():
                     help="time the big graphs at p = 0 and at every P, in place of the A/B of the matching")
     ap.add_argument("--columns", type=int, nargs="+", default=None, metavar="K",
                     help="time the big graphs with a scalar handle and a K-column handle per K, in place of the A/B of the matching")
+    ap.add_argument("--churn", type=float, default=None, metavar="F",
+                    help="time the big graphs without a topology, with everything alive and with a fraction F dead")
     a = ap.parse_args()
+    if a.churn is not None and (a.loss is not None or a.columns is not None or not 0.0 <= a.churn < 1.0):
+        ap.error("--churn takes a fraction in [0, 1) and does not combine with --loss or --columns")
     if a.columns is not None and (a.loss is not None or not all(1 <= k <= 16 for k in a.columns)):
         ap.error("--columns takes widths in 1..16 and does not combine with --loss")
     if a.rounds < 2:
@@ -326,6 +380,10 @@ def main():
     if not a.skip_replay:
         against_replay(a.rounds)
     copy_gbs = round(fu.copy_bandwidth(0), 1)
+    if a.churn is not None:
+        big_churn(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs, a.churn)
+        big_churn(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs, a.churn)
+        return
     if a.columns is not None:
         big_columns(f"er(n={a.n},m={4 * a.n},seed=1)", fu.Graph.erdos_renyi(a.n, 4 * a.n, seed=1), a.rounds, a.reps, copy_gbs, a.columns)
         big_columns(f"rr(n={a.n},d=8,seed=1)", fu.Graph.random_regular(a.n, 8, seed=1), a.rounds, a.reps, copy_gbs, a.columns)
