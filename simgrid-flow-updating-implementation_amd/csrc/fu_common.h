@@ -86,6 +86,15 @@ int pairing_rev(const std::string &who, int32_t n, int64_t e, const int64_t *row
                 const int32_t **rev, std::vector<int32_t> *built);
 }  // namespace fu
 
+// A HIP call that fails ends the calling entry point with FU_ERR_HIP and the call's text (the
+// device translation units; <hip/hip_runtime.h> is theirs to include).
+#define HIP_TRY(expr)                                                                     \
+  do {                                                                                    \
+    hipError_t _e = (expr);                                                               \
+    if (_e != hipSuccess)                                                                 \
+      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
+  } while (0)
+
 #define FU_TRY_BEGIN try {
 #define FU_TRY_END                                                   \
   }                                                                  \

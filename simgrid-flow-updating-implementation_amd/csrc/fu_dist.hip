@@ -20,11 +20,10 @@
 #include <string>
 #include <vector>
 
-#include "fu_common.h"
+#include "fu_ca_handle.h"
 
 using namespace fu;
 
-struct fu_handle;
 extern "C" int fu__create_common(int32_t n, int64_t e, const int64_t *rowptr, const int32_t *col,
                                  const double *value, int32_t device, int32_t a_extra, fu_handle **out);
 
@@ -67,16 +66,6 @@ __global__ void k_pack(long long cnt, const int *__restrict__ idx, const double 
 
 }  // namespace
 
-// Accessors implemented in fu_engine.hip (keeps fu_handle's layout private to that file).
-extern "C" void *fu__handle_dist(fu_handle *h);
-extern "C" void fu__handle_set_dist(fu_handle *h, void *d);
-extern "C" hipStream_t fu__handle_stream(fu_handle *h);
-extern "C" unsigned long long *fu__handle_err(fu_handle *h);
-extern "C" int fu__handle_device(fu_handle *h);
-extern "C" double *fu__handle_cur_a(fu_handle *h);
-extern "C" double *fu__handle_halo_a(fu_handle *h);
-extern "C" int64_t fu__handle_rounds(fu_handle *h);
-
 #define NCCL_TRY(expr)                                                                     \
   do {                                                                                     \
     ncclResult_t _r = (expr);                                                              \
@@ -95,12 +84,6 @@ int fu_dist_unique_id(uint8_t *id_out) {
   return FU_OK;
 }
 
-#define HIPD_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // phase 0: before a round (or a host sync): the main stream waits for the last halo.
 // phase 1: fu_reset: as phase 0, then the comm stream drains and the in-process transport's
 //   round bookkeeping restarts (round 0 may be packed and exchanged again).
@@ -112,13 +95,13 @@ int fu_dist_unique_id(uint8_t *id_out) {
 //   fu_dist_exchange_local queues the copies into the peers' ghost slots and their ev_halo.
 // phase 100 + k: all-reduce max of k error slots (on comm_stream, joined back).
 int fu__dist_round_hook(fu_handle *h, int phase) {
-  auto *d = static_cast<DistState *>(fu__handle_dist(h));
-  hipStream_t s = fu__handle_stream(h);
+  auto *d = static_cast<DistState *>(h->dist);
+  hipStream_t s = h->stream;
   if (phase == 0 || phase == 1) {
-    if (d->halo_pending) HIPD_TRY(hipStreamWaitEvent(s, d->ev_halo, 0));
+    if (d->halo_pending) HIP_TRY(hipStreamWaitEvent(s, d->ev_halo, 0));
     d->halo_pending = false;
     if (phase == 1) {
-      HIPD_TRY(hipStreamSynchronize(d->comm_stream));
+      HIP_TRY(hipStreamSynchronize(d->comm_stream));
       d->packed_round = d->exchanged_round = -1;
       d->timed_once = false;
     }
@@ -127,23 +110,23 @@ int fu__dist_round_hook(fu_handle *h, int phase) {
   if (phase >= 100) {
     if (!d->comm) return FU_OK;  // local transport: the caller combines the per-rank maxima
     const int k = phase - 100;
-    unsigned long long *err = fu__handle_err(h);
-    HIPD_TRY(hipEventRecord(d->ev_bnd, s));
-    HIPD_TRY(hipStreamWaitEvent(d->comm_stream, d->ev_bnd, 0));
+    unsigned long long *err = h->err;
+    HIP_TRY(hipEventRecord(d->ev_bnd, s));
+    HIP_TRY(hipStreamWaitEvent(d->comm_stream, d->ev_bnd, 0));
     NCCL_TRY(ncclAllReduce(err, err, (size_t)k, ncclUint64, ncclMax, d->comm, d->comm_stream));
-    HIPD_TRY(hipEventRecord(d->ev_halo, d->comm_stream));
-    HIPD_TRY(hipStreamWaitEvent(s, d->ev_halo, 0));
+    HIP_TRY(hipEventRecord(d->ev_halo, d->comm_stream));
+    HIP_TRY(hipStreamWaitEvent(s, d->ev_halo, 0));
     return FU_OK;
   }
-  double *a = fu__handle_halo_a(h);
+  double *a = h->halo_a;
   hipStream_t cs = d->comm_stream;
   if (d->comm && !d->any_halo) {  // nothing to exchange (one rank): no hop through the comm stream
     d->timed_once = true;
     return FU_OK;
   }
-  HIPD_TRY(hipEventRecord(d->ev_bnd, s));
-  HIPD_TRY(hipStreamWaitEvent(cs, d->ev_bnd, 0));
-  HIPD_TRY(hipEventRecord(d->ev_h0, cs));
+  HIP_TRY(hipEventRecord(d->ev_bnd, s));
+  HIP_TRY(hipStreamWaitEvent(cs, d->ev_bnd, 0));
+  HIP_TRY(hipEventRecord(d->ev_h0, cs));
   if (d->n_send_a > 0) {
     hipLaunchKernelGGL(k_pack, dim3((unsigned)((d->n_send_a + 255) / 256)), dim3(256), 0, cs,
                        (long long)d->n_send_a, d->send_a_idx, a, d->sbuf_a);
@@ -151,8 +134,8 @@ int fu__dist_round_hook(fu_handle *h, int phase) {
   hipError_t he = hipGetLastError();
   if (he != hipSuccess) return fail(FU_ERR_HIP, std::string("halo pack: ") + hipGetErrorString(he));
   if (!d->comm) {  // in-process transport: fu_dist_exchange_local moves the packed estimates
-    HIPD_TRY(hipEventRecord(d->ev_packed, cs));
-    d->packed_round = fu__handle_rounds(h);  // the round being launched
+    HIP_TRY(hipEventRecord(d->ev_packed, cs));
+    d->packed_round = h->rounds;  // the round being launched
     return FU_OK;
   }
   NCCL_TRY(ncclGroupStart());
@@ -164,8 +147,8 @@ int fu__dist_round_hook(fu_handle *h, int phase) {
     if (ra) NCCL_TRY(ncclRecv(a + d->n_local + d->recv_a_off[p], (size_t)ra, ncclDouble, p, d->comm, cs));
   }
   NCCL_TRY(ncclGroupEnd());
-  HIPD_TRY(hipEventRecord(d->ev_halo, cs));
-  HIPD_TRY(hipEventRecord(d->ev_h1, cs));
+  HIP_TRY(hipEventRecord(d->ev_halo, cs));
+  HIP_TRY(hipEventRecord(d->ev_h1, cs));
   d->timed_once = true;
   d->halo_pending = true;
   return FU_OK;
@@ -176,22 +159,22 @@ int fu__dist_round_hook(fu_handle *h, int phase) {
 // leaving its peers to block in the next halo exchange. Every rank must call it. The
 // in-process transport has one caller for all ranks, which sees every rank's result itself.
 int fu__dist_agree(fu_handle *h, int ok_local, int *ok_all) {
-  auto *d = static_cast<DistState *>(fu__handle_dist(h));
+  auto *d = static_cast<DistState *>(h->dist);
   *ok_all = ok_local;
   if (!d || !d->comm) return FU_OK;
-  if (!d->agree) HIPD_TRY(hipMalloc((void **)&d->agree, sizeof(unsigned long long)));
+  if (!d->agree) HIP_TRY(hipMalloc((void **)&d->agree, sizeof(unsigned long long)));
   unsigned long long v = ok_local ? 1ull : 0ull;
-  HIPD_TRY(hipStreamSynchronize(d->comm_stream));
-  HIPD_TRY(hipMemcpyAsync(d->agree, &v, sizeof(v), hipMemcpyHostToDevice, d->comm_stream));
+  HIP_TRY(hipStreamSynchronize(d->comm_stream));
+  HIP_TRY(hipMemcpyAsync(d->agree, &v, sizeof(v), hipMemcpyHostToDevice, d->comm_stream));
   NCCL_TRY(ncclAllReduce(d->agree, d->agree, 1, ncclUint64, ncclMin, d->comm, d->comm_stream));
-  HIPD_TRY(hipMemcpyAsync(&v, d->agree, sizeof(v), hipMemcpyDeviceToHost, d->comm_stream));
-  HIPD_TRY(hipStreamSynchronize(d->comm_stream));
+  HIP_TRY(hipMemcpyAsync(&v, d->agree, sizeof(v), hipMemcpyDeviceToHost, d->comm_stream));
+  HIP_TRY(hipStreamSynchronize(d->comm_stream));
   *ok_all = v != 0;
   return FU_OK;
 }
 
 void fu__dist_free(fu_handle *h) {
-  auto *d = static_cast<DistState *>(fu__handle_dist(h));
+  auto *d = static_cast<DistState *>(h->dist);
   if (!d) return;
   if (d->comm_stream) hipStreamSynchronize(d->comm_stream);
   if (d->comm) ncclCommDestroy(d->comm);
@@ -205,7 +188,7 @@ void fu__dist_free(fu_handle *h) {
   for (void *p : ptrs)
     if (p) hipFree(p);
   delete d;
-  fu__handle_set_dist(h, nullptr);
+  h->dist = nullptr;
 }
 
 static int dist_create(int32_t n_local, int64_t e_local, const int64_t *rowptr, const int32_t *col,
@@ -234,7 +217,7 @@ static int dist_create(int32_t n_local, int64_t e_local, const int64_t *rowptr, 
   fu_handle *h = nullptr;
   if (int rc = fu__create_common(n_local, e_local, rowptr, col, value, device, n_ghost_a, &h)) return rc;
   auto *d = new DistState();
-  fu__handle_set_dist(h, d);
+  h->dist = d;
   d->nranks = nranks;
   d->rank = rank;
   d->n_local = n_local;
@@ -309,15 +292,15 @@ int fu_dist_exchange_local(fu_handle **hs, int32_t nranks) {
   if (!hs || nranks < 1) return fail(FU_ERR_ARG, "fu_dist_exchange_local: bad arguments");
   std::vector<DistState *> ds(nranks);
   for (int p = 0; p < nranks; ++p) {
-    ds[p] = hs[p] ? static_cast<DistState *>(fu__handle_dist(hs[p])) : nullptr;
+    ds[p] = hs[p] ? static_cast<DistState *>(hs[p]->dist) : nullptr;
     if (!ds[p] || ds[p]->comm || ds[p]->rank != p || ds[p]->nranks != nranks)
       return fail(FU_ERR_ARG, "fu_dist_exchange_local: handle " + std::to_string(p) + " is not local-transport rank " +
                                   std::to_string(p) + " of " + std::to_string(nranks));
   }
   // every rank must have launched the same round r >= 0 and not yet exchanged its halo
-  const int64_t r = fu__handle_rounds(hs[0]) - 1;
+  const int64_t r = hs[0]->rounds - 1;
   for (int p = 0; p < nranks; ++p) {
-    if (fu__handle_rounds(hs[p]) - 1 != r || r < 0)
+    if (hs[p]->rounds - 1 != r || r < 0)
       return fail(FU_ERR_STATE, "fu_dist_exchange_local: ranks have run different numbers of rounds (or none)");
     if (ds[p]->packed_round != r || ds[p]->exchanged_round == r)
       return fail(FU_ERR_STATE, "fu_dist_exchange_local: round " + std::to_string(r) + " of rank " +
@@ -329,27 +312,27 @@ int fu_dist_exchange_local(fu_handle **hs, int32_t nranks) {
         return fail(FU_ERR_ARG, "fu_dist_exchange_local: halo plans of ranks " + std::to_string(p) + " and " +
                                     std::to_string(q) + " disagree");
   for (int q = 0; q < nranks; ++q) {
-    HIPD_TRY(hipSetDevice(fu__handle_device(hs[q])));
+    HIP_TRY(hipSetDevice(hs[q]->device));
     hipStream_t cs = ds[q]->comm_stream;
-    double *a = fu__handle_halo_a(hs[q]) + ds[q]->n_local;  // a_r of the round just launched
+    double *a = hs[q]->halo_a + ds[q]->n_local;  // a_r of the round just launched
     for (int p = 0; p < nranks; ++p) {
       const int64_t cnt = p == q ? 0 : ds[q]->recv_a_off[p + 1] - ds[q]->recv_a_off[p];
       if (!cnt) continue;
-      HIPD_TRY(hipStreamWaitEvent(cs, ds[p]->ev_packed, 0));
-      HIPD_TRY(hipMemcpyAsync(a + ds[q]->recv_a_off[p], ds[p]->sbuf_a + ds[p]->send_a_off[q], sizeof(double) * cnt,
-                              hipMemcpyDefault, cs));
+      HIP_TRY(hipStreamWaitEvent(cs, ds[p]->ev_packed, 0));
+      HIP_TRY(hipMemcpyAsync(a + ds[q]->recv_a_off[p], ds[p]->sbuf_a + ds[p]->send_a_off[q], sizeof(double) * cnt,
+                             hipMemcpyDefault, cs));
     }
-    HIPD_TRY(hipEventRecord(ds[q]->ev_halo, cs));
-    HIPD_TRY(hipEventRecord(ds[q]->ev_h1, cs));
+    HIP_TRY(hipEventRecord(ds[q]->ev_halo, cs));
+    HIP_TRY(hipEventRecord(ds[q]->ev_h1, cs));
     ds[q]->timed_once = true;
     ds[q]->halo_pending = true;
     ds[q]->exchanged_round = r;
   }
   for (int p = 0; p < nranks; ++p) {  // sbuf_a of p is free again once its receivers copied it
-    HIPD_TRY(hipSetDevice(fu__handle_device(hs[p])));
+    HIP_TRY(hipSetDevice(hs[p]->device));
     for (int q = 0; q < nranks; ++q)
       if (q != p && ds[p]->send_a_off[q + 1] > ds[p]->send_a_off[q])
-        HIPD_TRY(hipStreamWaitEvent(ds[p]->comm_stream, ds[q]->ev_halo, 0));
+        HIP_TRY(hipStreamWaitEvent(ds[p]->comm_stream, ds[q]->ev_halo, 0));
   }
   return FU_OK;
   FU_TRY_END
@@ -360,7 +343,7 @@ int fu_dist_exchange_local(fu_handle **hs, int32_t nranks) {
 // It overlaps the round's interior tiles. Waits for that halo.
 int fu_dist_halo_time(fu_handle *h, float *ms) {
   if (!h || !ms) return fail(FU_ERR_ARG, "fu_dist_halo_time: NULL argument");
-  auto *d = static_cast<DistState *>(fu__handle_dist(h));
+  auto *d = static_cast<DistState *>(h->dist);
   if (!d) return fail(FU_ERR_ARG, "fu_dist_halo_time: not a multi-GPU handle");
   if (!d->timed_once) return fail(FU_ERR_STATE, "fu_dist_halo_time: no halo exchanged yet");
   if (d->comm && !d->any_halo) {  // a rank with nothing to exchange
@@ -372,9 +355,9 @@ int fu_dist_halo_time(fu_handle *h, float *ms) {
   if (!d->comm && d->packed_round != d->exchanged_round)
     return fail(FU_ERR_STATE, "fu_dist_halo_time: round " + std::to_string(d->packed_round) +
                                   "'s halo is packed but not exchanged yet");
-  HIPD_TRY(hipSetDevice(fu__handle_device(h)));
-  HIPD_TRY(hipEventSynchronize(d->ev_h1));
-  HIPD_TRY(hipEventElapsedTime(ms, d->ev_h0, d->ev_h1));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(d->ev_h1));
+  HIP_TRY(hipEventElapsedTime(ms, d->ev_h0, d->ev_h1));
   return FU_OK;
 }
 

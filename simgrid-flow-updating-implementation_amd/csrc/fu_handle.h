@@ -25,13 +25,6 @@
 
 #include "fu_common.h"
 
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return fu::fail(FU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
-
 namespace fu {
 
 using u64 = unsigned long long;

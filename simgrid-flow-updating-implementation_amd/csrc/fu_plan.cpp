@@ -1,5 +1,5 @@
 // Host-side launch plans of the collect-all round kernels (see fu_plan.h). No HIP here: the
-// engine (fu_engine.hip) uploads what these functions build, and tools/plan_check.cpp runs
+// engine (fu_ca_layout.h) uploads what these functions build, and tools/plan_check.cpp runs
 // them under ASan/UBSan against a CPU replay of the kernels' indexing.
 #include "fu_plan.h"
 

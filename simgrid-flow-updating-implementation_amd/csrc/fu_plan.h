@@ -1,4 +1,4 @@
-// Host-side launch plans of the collect-all round kernels (fu_engine.hip), as pure C++ with no
+// Host-side launch plans of the collect-all round kernels (fu_ca_*.h), as pure C++ with no
 // HIP dependency: the kernel 4 tile lists per geometry (mega hubs, heavy rows, light tiles, the
 // trailing degree-0 rows), the mega-hub side tables, kernel 8's slice layouts and kernel 9's
 // staging and transpose tables, and the launch partition of a kernel-9 round (which launch

@@ -52,7 +52,7 @@ def handle_info(h) -> dict:
                                   enumerate(TUNE_CANDIDATES)}}
 
 
-# fu_engine.hip kCands order
+# fu_plan.h kCands order
 TUNE_CANDIDATES = ("recon", "recon_512", "stage", "recon_1024", "pregather")
 
 

@@ -7,7 +7,7 @@ default cut and take it from there); values are fu.uniform_values at VALUE_SEED;
 fu_set_option keys the case runs with. Numpy and the host graph code only: nothing here
 touches a GPU.
 
-The per-rank counts these cuts drive to their edges (fu_plan.cpp, fu_engine.hip's launchers,
+The per-rank counts these cuts drive to their edges (fu_plan.cpp, fu_ca_launch.h's launchers,
 fu_dist.hip): the number of boundary light tiles 0 or all of them, no light tile at all, an
 empty send list, a zero-count middle peer, many more ghost slots than rows, no edge.
 """

@@ -3,7 +3,7 @@ and under option switches), shared with the CPU checks of their conditions in
 tests/test_pack_case_inputs.py. Numpy, the host graph generators and the C oracle only:
 nothing here touches a GPU.
 
-The table (fu_engine.hip, "Packed estimate table"): an estimate a is stored as the code
+The table (fu_ca_pack.h, "Packed estimate table"): an estimate a is stored as the code
 off = dkey(a) - base when 0 <= off < esc (esc = 2^W - 1), else as the escape code esc, whose
 reader gathers the double; base = centre - 2^(W-1). The plan takes the centre (the median key
 of the first 64 sampled gather targets) and the width (the narrowest W whose window holds

@@ -2,8 +2,8 @@
 path and partition, bit for bit against values worked out from the C oracle alone.
 
 The scalar engine has no error kernel of its own for rounds >= 1: every round launch carries
-a CHECK branch (csrc/fu_engine.hip: light tiles, heavy rows per wave and per block, the
-mega-hub chain block, kernel 8's staged tiles, kernel 9's k_heavy_multi and k_isolated, the
+a CHECK branch (csrc/fu_ca_recon.h, fu_ca_stage.h, fu_ca_pregather.h: light tiles, heavy rows
+per wave and per block, the mega-hub chain block, kernel 8's staged tiles, kernel 9's k_heavy_multi and k_isolated, the
 PART boundary / interior launches of partitioned handles), each reducing its own rows into
 one slot. With component means as targets nothing controls which row holds the maximum, so
 a launch that drops its rows, or one that adds something it should not, goes unseen.

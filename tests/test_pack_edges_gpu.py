@@ -1,4 +1,4 @@
-"""The packed estimate table (fu_engine.hip: put_code, ld_est, gather_packed, k_stage,
+"""The packed estimate table (fu_ca_pack.h: put_code, ld_est, gather_packed; k_stage,
 k_hub_flows, kernel 9's staging) where it is least comfortable: estimates planted on the
 edges of the code window, and options, resets and readbacks at a packed width. The inputs
 are tests/pack_cases.py; tests/test_pack_case_inputs.py holds them to their conditions on the

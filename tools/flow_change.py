@@ -1,6 +1,6 @@
 """How much of each flow changes from f_{r-2} to f_r, round by round (CPU, C oracle).
 
-The engine stores a flow as three pieces (csrc/fu_engine.hip, f_idx): the high 32-bit word,
+The engine stores a flow as three pieces (csrc/fu_ca_recon.h, fhi_idx): the high 32-bit word,
 the middle and the low 16 bits of the low word, each rewritten only when it changes. This
 tool counts, per round, the directed edges whose f_r equals f_{r-2} bit for bit, whose high
 word is unchanged, and whose change stays inside the low 16 bits (the edges a round then

@@ -4,7 +4,8 @@
 // table is checked without a GPU. Built with -fsanitize=address,undefined (tools/Makefile), so
 // the builders themselves run under ASan/UBSan too. Run by tests/test_plan_check.py.
 //
-// Checked, per graph and option set (the kernels' reads and writes, fu_engine.hip):
+// Checked, per graph and option set (the kernels' reads and writes, fu_ca_recon.h, fu_ca_stage.h,
+// fu_ca_pregather.h):
 //   * k_round0_flows: blk_row, the row search of every 4-edge group;
 //   * kernel 4 tiles of the four geometries: every row computed by exactly one launch (mega-hub
 //     chains, heavy tiles, light tiles), every flow written once (k_hub_flows for the hubs),
